@@ -1,10 +1,14 @@
 """Benchmark of the LW-DETR inference hot path on MI355X (contract: see the task's bench.py section).
 
-    python bench.py [--gpus N --steps K --warmup W]          # N=1: LW-DETR-small, 640x640, batch 32, fp16
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]    # N=1: LW-DETR-small, 640x640, batch 32, fp16
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" = one forward of the HIP path over one resident synthetic batch (images already in HBM) + PostProcess
 (+ the RCCL all-gather of detections when N > 1; weak scaling: the per-GPU batch is fixed). Prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds what takes runs of its own (after the
+timed region, never part of `value`): three more passes of the K steps and GPU telemetry, the per-kernel roofline pass,
+single-image latency, the other BASELINE configurations and the CPU baseline (each can be left out by its --no-* flag).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; inputs are seeded).
 """
 import argparse
 import json
@@ -40,9 +44,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--res", type=int, default=640)
     ap.add_argument("--dtype", default="fp16", choices=list(DTYPES))
+    ap.add_argument("--full", action="store_true", help="also run the measurements beside the headline figure: extra passes + telemetry, "
+                    "roofline, latency, other configurations, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--latency", action="store_true", help="also report p50/p90 single-image latency (bs=1); on by default at N=1")
+    ap.add_argument("--latency", action="store_true", help="with --full: also report p50/p90 single-image latency (bs=1); on by default at N=1")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-image latency measurement")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of the other BASELINE configurations (N=1 default workload only)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
@@ -315,6 +322,39 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 60 * 2 ** 20          # under 64 MB however counted, .npy headers included
+
+
+def dump_outputs(out_dir, out, det):
+    """What a caller of the timed step receives - the output dict of LWDETR.detect (flattened to dotted names) and the (B, K, 6)
+    detection records - as <out_dir>/<name>.npy in float32. Every array is indexed by image along dim 0; when the whole set would
+    exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of images is kept from each."""
+    import numpy as np
+    arrays = {}
+
+    def flat(prefix, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                flat(f"{prefix}.{k}" if prefix else k, x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                flat(f"{prefix}.{i}", x)
+        else:
+            arrays[prefix] = v
+    flat("", out)
+    arrays["detections"] = det
+    total = sum(t.numel() * 4 for t in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            n = t.shape[0]
+            keep = max(1, n * DUMP_LIMIT_BYTES // total)
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step -> {out_dir} ({len(arrays)} arrays)")
+
+
 # ---- GPU telemetry beside the timed region (round 6; VERDICT r5 item 6a): the boxes of this pool differ by 12-15 % on the same tree and the record
 # carried no clock, power or temperature to tell a slow draw from a slow tree. Read from the card's sysfs hwmon files (no subprocess, nothing on the GPU - but milliseconds per sample:
 # never between the warm-up and the timed region); `rocm-smi --json` once as the fallback. All failures are swallowed: telemetry never costs the line.
@@ -437,7 +477,8 @@ def main():
         return _cpu_baseline_worker(a)
     if a.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         return self_launch(a)                       # started plainly: become the launcher of N ranks
-    rank, world, local = ldist.init_from_env(rccl_log=True)      # opt-in: config.rccl reports the channel transports
+    # --launch-check is the CPU / gloo check of the launch path: gloo even where a GPU is visible (nccl would put every rank on it)
+    rank, world, local = ldist.init_from_env(backend="gloo" if a.launch_check else None, rccl_log=True)      # opt-in: config.rccl reports the channel transports
     if world != a.gpus:
         raise SystemExit(f"bench.py: --gpus {a.gpus} but the process group has {world} rank(s); refusing to report")
     if a.launch_check:
@@ -464,8 +505,8 @@ def main():
     gathered = torch.empty(world * a.batch, cfg.num_select, 6, dtype=torch.float32, device=dev) if grouped else None
 
     def step():
-        _out, det = model.detect(images, sizes, pp)       # forward + PostProcess -> (B, K, 6) records
-        return ldist.all_gather_detections(det, gathered, always_collective=grouped)
+        out, det = model.detect(images, sizes, pp)        # forward + PostProcess -> (output dict, (B, K, 6) records)
+        return out, ldist.all_gather_detections(det, gathered, always_collective=grouped)
 
     def barrier():
         if grouped:
@@ -475,7 +516,7 @@ def main():
     # telemetry sample 1: BEFORE the warm-up. (Round 6 first put it between the warm-up and the timed region: reading seven hwmon files is
     # milliseconds of idle GPU right in front of the region, and the same-box A/B against the round-5 tree showed the reported first pass 0.8 %
     # (config 2) / 1.7 % (tiny) slower while every later pass was equal - profiles/r6d_*. The instrument must not touch what it measures.)
-    tele_before = gpu_telemetry() if rank == 0 else {}
+    tele_before = gpu_telemetry() if (rank == 0 and a.full) else {}
     log(f"model built ({a.size}, {a.dtype}); warm-up x{a.warmup}")
     for _ in range(a.warmup):
         step()
@@ -483,15 +524,18 @@ def main():
     log("timing")
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        det = step()
+        out, det = step()
     barrier()
     dt = time.perf_counter() - t0
-    tele_after = gpu_telemetry() if rank == 0 else {}
+    tele_after = gpu_telemetry() if (rank == 0 and a.full) else {}
     dt_nog = None
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = tt.item()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, det)
+    if world > 1 and a.full:
         # the same steps without the collective (outside the reported region): what the all-gather costs
         barrier()
         t1 = time.perf_counter()
@@ -505,11 +549,11 @@ def main():
     log(f"timed {a.steps} steps: {dt / a.steps * 1e3:.3f} ms/step")
     ms_step = dt / a.steps * 1e3
     ips = world * a.batch * a.steps / dt
-    # three more passes of the same K steps AFTER the reported region (never part of `value`): a slow draw of the box or of the one
+    # --full: three more passes of the same K steps AFTER the reported region (never part of `value`): a slow draw of the box or of the one
     # timed region shows in the record
     extra_passes = []
     tele_load = {}
-    for ip in range(4):
+    for ip in range(4 if a.full else 0):
         barrier()
         sampler = TelemetrySampler().start() if (rank == 0 and ip == 3) else None       # a FOURTH pass carries the sampling thread (clocks / power under load) and is not listed:
                                                                                         # the thread costs that pass ~1 % (profiles/r6d_*)
@@ -535,18 +579,20 @@ def main():
                    "collective": "all_gather_into_tensor of (B,K,6) f32 detections" if grouped else "none", "backend": backend,
                    "launch_chains": type(model)._chains_for(a.batch, a.res, a.res)},
     }
-    all_ms = sorted([ms_step] + [t / a.steps * 1e3 for t in extra_passes])
-    result["ms_per_step_passes"] = {"timed": round(ms_step, 3), "after": [round(t / a.steps * 1e3, 3) for t in extra_passes],
-                                    "median_of_all": round((all_ms[1] + all_ms[2]) / 2, 3), "median_images_per_sec": round(world * a.batch / ((all_ms[1] + all_ms[2]) / 2) * 1e3, 1),
-                                    "note": "value / ms_per_step come from `timed` alone; `after` = three more passes of the same K steps outside the timed region; "
-                                            "median_* = over the four (a fifth pass, not listed, carries the telemetry sampling thread)"}
+    if a.full:
+        all_ms = sorted([ms_step] + [t / a.steps * 1e3 for t in extra_passes])
+        result["ms_per_step_passes"] = {"timed": round(ms_step, 3), "after": [round(t / a.steps * 1e3, 3) for t in extra_passes],
+                                        "median_of_all": round((all_ms[1] + all_ms[2]) / 2, 3), "median_images_per_sec": round(world * a.batch / ((all_ms[1] + all_ms[2]) / 2) * 1e3, 1),
+                                        "note": "value / ms_per_step come from `timed` alone; `after` = three more passes of the same K steps outside the timed region; "
+                                                "median_* = over the four (a fifth pass, not listed, carries the telemetry sampling thread)"}
     try:
         pr = torch.cuda.get_device_properties(dev)
         import hashlib, socket
         result["config"]["box"] = {"device": pr.name, "cus": pr.multi_processor_count, "mem_gb": round(pr.total_memory / 2 ** 30),
                                    "clock_mhz": getattr(pr, "clock_rate", 0) // 1000, "gcn_arch": getattr(pr, "gcnArchName", ""),
-                                   "host": hashlib.sha1(socket.gethostname().encode()).hexdigest()[:8],
-                                   "telemetry": {"before_warmup": tele_before, "after_timed_region": tele_after, "under_load_extra_pass": tele_load}}
+                                   "host": hashlib.sha1(socket.gethostname().encode()).hexdigest()[:8]}
+        if a.full:
+            result["config"]["box"]["telemetry"] = {"before_warmup": tele_before, "after_timed_region": tele_after, "under_load_extra_pass": tele_load}
     except Exception as e:                      # never fail the line over a label
         result["config"]["box"] = {"error": str(e)[:80]}
     if rank == 0 and backend == "nccl":
@@ -558,7 +604,7 @@ def main():
         result["model_tflops"] = round(ips * gf / 1e3, 2)
         result["model_mfma_frac"] = round(ips * gf / 1e3 / (PEAK_TFLOPS[a.dtype] * world), 4)
 
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         # dedicated pass with per-kernel HIP events on the launch stream (outside the timed region). The timed region runs a
         # batch of >= 32 images as two launch chains on two streams (LWDETR._forward_chains); a kernel's duration measured
         # while the other chain shares the chip says nothing about the kernel, so this pass runs ONE chain: per-kernel figures
@@ -610,8 +656,8 @@ def main():
         result["roofline"] = roof
         result["kernels"] = table
 
-    # single-image latency (after the timed region; ~1 s): reported by default at N=1, on request otherwise
-    if rank == 0 and (a.latency or world == 1) and not a.no_latency:
+    # --full: single-image latency (after the timed region; ~1 s): reported by default at N=1, on request otherwise
+    if rank == 0 and a.full and (a.latency or world == 1) and not a.no_latency:
         one = images[:1].contiguous()
 
         def p50p90(fn):
@@ -638,7 +684,7 @@ def main():
             result["latency_bs1_hipgraph_ms"] = {"error": repr(e)[:200]}
 
     default_workload = (a.size, a.batch, a.res, a.dtype) == ("small", 32, 640, "fp16")
-    if rank == 0 and world == 1 and default_workload and not a.no_other_configs:
+    if rank == 0 and a.full and world == 1 and default_workload and not a.no_other_configs:
         # the other BASELINE configurations (and tiny) on this GPU, 20 steps each: config 3 as stated, configs 4 / 5 as the per-GPU shard
         result["other_configs"] = {}
         for (sz, bt, rs, dt_) in OTHER_CONFIGS:
@@ -648,7 +694,7 @@ def main():
             except Exception as e:                                   # never let the extra measurement cost the bench line
                 result["other_configs"][f"{sz}_b{bt}_{rs}_{dt_}"] = {"error": repr(e)[:200]}
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and world == 1 and not a.no_cpu_baseline:
         log("cpu baseline (child process)")
         result["cpu_baseline"] = cpu_baseline(a.size, a.res)
 
