@@ -153,6 +153,13 @@ int lwdetr_has_experiments(void);
 void lwdetr_gemm_pt_tuning(int pt_mode);
 /* launches of the persistent kernel by this process so far (tests assert which kernel served a shape) */
 long lwdetr_gemm_pt_count(void);
+/* Launch-path record of lwdetr_gemm and lwdetr_gemm_few: one process-wide host counter per kernel family, tile and variant (the 64 x 64 ring at
+ * each depth, 128 x 64, 128 x 128; the large-tile kernel per column tile and stage depth; the persistent kernel; the few-row kernel's PLAIN and
+ * CONV forms ...), incremented after a launch was issued and accepted - a refused request counts nothing. lwdetr_gemm_path_counts copies the
+ * first min(n, count) counters to out (out may be NULL) and returns count; lwdetr_gemm_path_name(i) is the family name of counter i (NULL
+ * outside [0, count)). Tests assert which kernel served a launch. */
+int lwdetr_gemm_path_counts(long* out, int n);
+const char* lwdetr_gemm_path_name(int i);
 
 /* ---- fused softmax(QK^T)V, flash-style, MFMA ------------------------------------------------------------------- */
 typedef struct {

@@ -18,6 +18,7 @@ DT_F32, DT_F16, DT_BF16, DT_F64 = 0, 1, 2, 3
 A_PLAIN, A_CONV3x3, A_PATCH16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SILU = 0, 1, 2, 3
 OUT_LINEAR, OUT_HEADS, OUT_HEADS_T, OUT_TOKMAP, OUT_DECONV2x2 = 0, 1, 2, 3, 4
+ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3
 ERRORS = {-1: "bad argument", -2: "unsupported configuration", -3: "kernel launch failed"}
 
 
@@ -94,6 +95,9 @@ def lib():
         l.lwdetr_gemm_pt_tuning.restype = None
         l.lwdetr_gemm_pt_count.argtypes = []
         l.lwdetr_gemm_pt_count.restype = C.c_long
+        l.lwdetr_gemm_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_gemm_path_name.argtypes = [i]
+        l.lwdetr_gemm_path_name.restype = C.c_char_p
         l.lwdetr_attention_tuning.argtypes = [i]
         l.lwdetr_attention_tuning.restype = None
         l.lwdetr_attention_tuning_cfg.argtypes = [i]
@@ -180,6 +184,15 @@ def require_cuda(*tensors):
 
 
 # ----------------------------------------------------------------------------------------------- profiling
+def gemm_path_counts() -> dict:
+    """{kernel family name: launches so far} of lwdetr_gemm / lwdetr_gemm_few in this process (lwdetr_gemm_path_counts)."""
+    l = lib()
+    n = l.lwdetr_gemm_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_gemm_path_counts(buf, n)
+    return {l.lwdetr_gemm_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
 def tuning_set(name: str, value=None):
     """Override (value: int) or clear (None) one launch-path switch of the library (lwdetr_tuning_set; the LWDETR_* environment is read once per
     process, so tests and tools that switch inside a process go through here)."""

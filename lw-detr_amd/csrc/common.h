@@ -168,3 +168,14 @@ static inline int lwdetr_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? LWDETR_OK : LWDETR_ERR_LAUNCH;
 }
+
+// ---- launch-path record of lwdetr_gemm / lwdetr_gemm_few (lwdetr_gemm_path_counts): one host counter per kernel family, tile and variant,
+// counted after the launch was issued and accepted; a request the dispatcher refuses counts nothing. Names: gemm.hip, kGemmPathNames.
+enum {
+    GP_PLAIN_64x64 = 0, GP_PLAIN_128x64, GP_PLAIN_128x128,
+    GP_RING_64x64_D2, GP_RING_64x64_D3, GP_RING_64x64_D4, GP_RING_64x64_D3_KB64, GP_RING_64x64_SPLITK, GP_RING_128x64, GP_RING_128x128_D3,
+    GP_RING_128x128_D4, GP_CONV_PATCH_128, GP_CONV_PATCH_192,
+    GP_BIG_256_KB64, GP_BIG_256_KB32, GP_BIG_192_KB64, GP_BIG_128_KB64, GP_BIG_128_KB32, GP_BIG4_256, GP_BIG4_192, GP_BIG_LN,
+    GP_PT, GP_FEW_PLAIN, GP_FEW_CONV_KCH4, GP_FEW_CONV_KCH6, GP_COUNT
+};
+int lwdetr_gemm_path_done(int path, int rc);     // counts `path` when rc == LWDETR_OK; returns rc

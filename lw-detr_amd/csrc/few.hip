@@ -97,12 +97,13 @@ int few_launch(const lwdetr_gemm_desc& d, hipStream_t st) {
     const dim3 block((unsigned)(64 * nwv));
     const int kid = d.a_mode == LWDETR_A_CONV3x3 ? KID_GEMM_CONV : KID_GEMM;
     ProfScope ps(kid, 2.0 * d.M * d.N * d.K, ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N) * sizeof(T), st);
+    int path = GP_FEW_PLAIN;
     if (d.a_mode == LWDETR_A_CONV3x3) {
         // a batch = the three taps of one kernel row (3 x Cin / 32 chunks): Cin = 128 -> 12, Cin = 192 -> 18
-        if (d.conv_cin == 192) hipLaunchKernelGGL((gemm_few_kernel<T, LWDETR_A_CONV3x3, 6>), grid, block, 0, st, d);
-        else hipLaunchKernelGGL((gemm_few_kernel<T, LWDETR_A_CONV3x3, 4>), grid, block, 0, st, d);
+        if (d.conv_cin == 192) { hipLaunchKernelGGL((gemm_few_kernel<T, LWDETR_A_CONV3x3, 6>), grid, block, 0, st, d); path = GP_FEW_CONV_KCH6; }
+        else { hipLaunchKernelGGL((gemm_few_kernel<T, LWDETR_A_CONV3x3, 4>), grid, block, 0, st, d); path = GP_FEW_CONV_KCH4; }
     } else hipLaunchKernelGGL((gemm_few_kernel<T, LWDETR_A_PLAIN, 4>), grid, block, 0, st, d);
-    return lwdetr_check_launch();
+    return lwdetr_gemm_path_done(path, lwdetr_check_launch());
 }
 
 }  // namespace
@@ -113,6 +114,11 @@ extern "C" int lwdetr_gemm_few(const lwdetr_gemm_desc* desc, int dtype, void* hi
     if (d.M < 0 || d.N <= 0 || d.K <= 0 || !d.A || !d.W || d.nseg != 1 || !d.seg[0].out || d.seg[0].n_begin != 0) return LWDETR_ERR_BAD_ARG;
     if (d.M == 0) return LWDETR_OK;
     const lwdetr_gemm_seg& g = d.seg[0];
+    if (g.act < LWDETR_ACT_NONE || g.act > LWDETR_ACT_SILU) return LWDETR_ERR_BAD_ARG;
+    // what the kernel reads and writes in wide pieces: bias / gamma 16-byte loads, residual / second destination / out 8-byte runs of 4;
+    // columns [N, n_end) would never be written (lwdetr_gemm serves those descriptors)
+    if (g.n_end != d.N || ((size_t)g.bias & 15) != 0 || ((size_t)g.gamma & 15) != 0 || ((size_t)g.res & 7) != 0 || ((size_t)g.out2 & 7) != 0)
+        return LWDETR_ERR_UNSUPPORTED;
     if ((dtype != DT_F16 && dtype != DT_BF16) || d.A2 || d.M > 8192 || d.K % 32 != 0 || d.N % 16 != 0 || g.mode != LWDETR_OUT_LINEAR || g.rowmask || g.ln_stats ||
         g.res_mod > 0 || g.n_end < d.N || g.ldo % 4 != 0 || (g.res && g.ldres % 4 != 0) || (g.out2 && g.ld2 % 4 != 0) || d.lda % 8 != 0 ||
         ((size_t)d.A & 15) != 0 || ((size_t)d.W & 15) != 0 || ((size_t)g.out & 7) != 0)

@@ -17,6 +17,7 @@
 // Workgroup ids are remapped so that tiles sharing an A row-panel run on the same XCD (private L2).
 #include "common.h"
 #include <cstdlib>
+#include <atomic>
 #include <type_traits>
 
 // gemm_pt.hip: launches the persistent large-tile kernel if the shape is one of its own (taken = true), otherwise leaves the launch to this file
@@ -1575,7 +1576,12 @@ int launch_big(const lwdetr_gemm_desc& d, hipStream_t st) {
     else
 #endif
     hipLaunchKernelGGL((gemm_big_kernel<T, BN, KB, NST, AMODE>), dim3((unsigned)nwg), dim3(512), lds, st, d);
-    return lwdetr_check_launch();
+    constexpr int path = LN ? GP_BIG_LN
+                       : NW == 4 ? (BN == 256 ? GP_BIG4_256 : GP_BIG4_192)
+                       : BN == 256 ? (KB == 64 ? GP_BIG_256_KB64 : GP_BIG_256_KB32)
+                       : BN == 192 ? GP_BIG_192_KB64 : (KB == 64 ? GP_BIG_128_KB64 : GP_BIG_128_KB32);
+    static_assert(NW == 4 || BN != 192 || KB == 64, "one 192-wide 8-wave form");
+    return lwdetr_gemm_path_done(path, lwdetr_check_launch());
 }
 
 // Shapes the large-tile kernel takes: plain A or the implicit-GEMM 3x3 view, no A2, K (and Cin) a multiple of 64, segment
@@ -1634,7 +1640,7 @@ int try_launch_big(const lwdetr_gemm_desc& d, hipStream_t st, bool& taken) {
         else if (wg2 && bn == 192) rc = launch_big<T, 192, 32, 3, AMODE, 128, 4>(d, st);
         else
 #else
-        if (wg2 && bn != 128) return LWDETR_ERR_UNSUPPORTED;       // the 4-wave form was asked for by name: not in this build
+        (void)wg2;      // the 4-wave form is not in this build: a request for it by name (tuning 128, LWDETR_GEMM_BIG_2WG=2) gets the 8-wave kernel
 #endif
         if (bn == 256) rc = variant == 32 ? launch_big<T, 256, 32, 4, AMODE>(d, st) : launch_big<T, 256, 64, 2, AMODE>(d, st);
         else if (bn == 192) rc = launch_big<T, 192, 64, 2, AMODE>(d, st);
@@ -1666,7 +1672,7 @@ int launch_conv_patch(const lwdetr_gemm_desc& d, hipStream_t st) {
     const unsigned hw = (unsigned)(d.conv_hout * d.conv_wout);
     hipLaunchKernelGGL((conv3x3_patch_kernel<T, CIN, CIN, NST>), dim3((unsigned)nwg), dim3(256), lds, st, d, np,
                        (unsigned)(0x100000000ull / hw), (unsigned)(0x100000000ull / (unsigned)d.conv_wout));
-    return lwdetr_check_launch();
+    return lwdetr_gemm_path_done(CIN == 128 ? GP_CONV_PATCH_128 : GP_CONV_PATCH_192, lwdetr_check_launch());
 }
 
 template <typename T>
@@ -1752,30 +1758,35 @@ int launch(const lwdetr_gemm_desc& d, hipStream_t st) {
             // (N 256, K 768) 60 -> 137 us, value projection (N 768, K 256) 62 -> 93 / 124 us. It cuts what a CU pulls in by 2-3x
             // and loses anyway: with 66-108 KB of LDS a CU holds one or two workgroups whose column tiles, epilogues and store
             // latencies run back to back, where the 64 x 64 grid keeps 4-5 independent workgroups per CU in flight.)
-            if (small && kb64) hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 3, 64>), dim3((unsigned)nwg), dim3(256), 0, st, d);
+            int path;
+            if (small && kb64) { hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 3, 64>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_RING_64x64_D3_KB64; }
             else if (small) {
                 // ring depth of the 64 x 64 kernel trades prefetch distance against workgroups per CU (24 KB of LDS at depth 3:
                 // six per CU). Measured on the whole network: depth 4 0.894 ms, depth 3 0.847 ms, depth 2 0.868 ms per step.
                 const int nst = (int)lwdetr_knob(KNOB_GEMM_NST, 3);
-                if (nst == 2) hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 2>), dim3((unsigned)nwg), dim3(256), 0, st, d);
+                if (nst == 2) { hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 2>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_RING_64x64_D2; }
 #ifdef LWDETR_EXPERIMENTS
-                else if (nst == 3 && d.splitk >= 2 && d.splitk_ws && d.K / 32 >= d.splitk)          // round 5: few rows, long K (see gemm_dma_kernel)
+                else if (nst == 3 && d.splitk >= 2 && d.splitk_ws && d.K / 32 >= d.splitk) {         // round 5: few rows, long K (see gemm_dma_kernel)
                     hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 3, 32, true>), dim3((unsigned)(nwg * d.splitk)), dim3(256), 0, st, d);
+                    path = GP_RING_64x64_SPLITK;
+                }
 #endif
-                else if (nst == 3) hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 3>), dim3((unsigned)nwg), dim3(256), 0, st, d);
-                else hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 4>), dim3((unsigned)nwg), dim3(256), 0, st, d);
+                else if (nst == 3) { hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 3>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_RING_64x64_D3; }
+                else { hipLaunchKernelGGL((gemm_dma_kernel<T, 64, 64, AMODE, 4>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_RING_64x64_D4; }
             }
-            else if (bn64) hipLaunchKernelGGL((gemm_dma_kernel<T, 128, 64, AMODE, 4>), dim3((unsigned)nwg), dim3(256), 0, st, d);
-            else if (mode == 4) hipLaunchKernelGGL((gemm_dma_kernel<T, 128, 128, AMODE, 4>), dim3((unsigned)nwg), dim3(256), 0, st, d);
-            else hipLaunchKernelGGL((gemm_dma_kernel<T, 128, 128, AMODE, 3>), dim3((unsigned)nwg), dim3(256), 0, st, d);
-            return lwdetr_check_launch();
+            else if (bn64) { hipLaunchKernelGGL((gemm_dma_kernel<T, 128, 64, AMODE, 4>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_RING_128x64; }
+            else if (mode == 4) { hipLaunchKernelGGL((gemm_dma_kernel<T, 128, 128, AMODE, 4>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_RING_128x128_D4; }
+            else { hipLaunchKernelGGL((gemm_dma_kernel<T, 128, 128, AMODE, 3>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_RING_128x128_D3; }
+            return lwdetr_gemm_path_done(path, lwdetr_check_launch());
         }
     }
-    if (small) hipLaunchKernelGGL((gemm_kernel<T, 64, 64, AMODE>), dim3((unsigned)nwg), dim3(256), 0, st, d);
-    else if (bn64) hipLaunchKernelGGL((gemm_kernel<T, 128, 64, AMODE>), dim3((unsigned)nwg), dim3(256), 0, st, d);
+    int path = GP_PLAIN_128x128;
+    if (small) { hipLaunchKernelGGL((gemm_kernel<T, 64, 64, AMODE>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_PLAIN_64x64; }
+    else if (bn64) { hipLaunchKernelGGL((gemm_kernel<T, 128, 64, AMODE>), dim3((unsigned)nwg), dim3(256), 0, st, d); path = GP_PLAIN_128x64; }
     else if constexpr (sizeof(T) == 2)
         hipLaunchKernelGGL((gemm_kernel<T, 128, 128, AMODE>), dim3((unsigned)nwg), dim3(256), 0, st, d);
-    return lwdetr_check_launch();
+    else return LWDETR_ERR_UNSUPPORTED;      // (f32 tiles are 128 x 64: bn64 is always set)
+    return lwdetr_gemm_path_done(path, lwdetr_check_launch());
 }
 
 template <typename T>
@@ -1789,6 +1800,26 @@ int dispatch_amode(const lwdetr_gemm_desc& d, hipStream_t st) {
 }
 
 }  // namespace
+
+namespace {
+std::atomic<long> g_gemm_path[GP_COUNT];
+const char* const kGemmPathNames[GP_COUNT] = {
+    "gemm_kernel_64x64", "gemm_kernel_128x64", "gemm_kernel_128x128",
+    "gemm_dma_64x64_d2", "gemm_dma_64x64_d3", "gemm_dma_64x64_d4", "gemm_dma_64x64_d3_kb64", "gemm_dma_64x64_splitk", "gemm_dma_128x64",
+    "gemm_dma_128x128_d3", "gemm_dma_128x128_d4", "conv3x3_patch_128", "conv3x3_patch_192",
+    "gemm_big_256_kb64", "gemm_big_256_kb32", "gemm_big_192_kb64", "gemm_big_128_kb64", "gemm_big_128_kb32", "gemm_big4_256", "gemm_big4_192",
+    "gemm_big_ln", "gemm_pt", "gemm_few_plain", "gemm_few_conv_kch4", "gemm_few_conv_kch6"};
+}  // namespace
+
+int lwdetr_gemm_path_done(int path, int rc) {
+    if (rc == LWDETR_OK && path >= 0 && path < GP_COUNT) g_gemm_path[path].fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
+extern "C" int lwdetr_gemm_path_counts(long* out, int n) {
+    for (int i = 0; out && i < n && i < GP_COUNT; ++i) out[i] = g_gemm_path[i].load(std::memory_order_relaxed);
+    return GP_COUNT;
+}
+extern "C" const char* lwdetr_gemm_path_name(int i) { return i >= 0 && i < GP_COUNT ? kGemmPathNames[i] : nullptr; }
 
 extern "C" void lwdetr_gemm_tuning(int big_mode) { g_big_mode = big_mode; }
 extern "C" int lwdetr_has_experiments(void) {
@@ -1810,6 +1841,7 @@ extern "C" int lwdetr_gemm(const lwdetr_gemm_desc* desc, int dtype, void* hip_st
     for (int s = 0; s < d.nseg; ++s) {
         const lwdetr_gemm_seg& g = d.seg[s];
         if (!g.out || g.n_end <= g.n_begin) return LWDETR_ERR_BAD_ARG;
+        if (g.act < LWDETR_ACT_NONE || g.act > LWDETR_ACT_SILU) return LWDETR_ERR_BAD_ARG;     // the kernels disagree on anything else
         if (s + 1 < d.nseg && d.seg[s + 1].n_begin != g.n_end) return LWDETR_ERR_BAD_ARG;
         if ((g.mode == LWDETR_OUT_HEADS || g.mode == LWDETR_OUT_HEADS_T) &&
             (g.p0 <= 0 || g.p1 <= 0 || g.p2 <= 0 || g.p1 % 4 != 0 || g.p0 % 4 != 0)) return LWDETR_ERR_BAD_ARG;

@@ -494,7 +494,7 @@ int pt_launch(const lwdetr_gemm_desc& d, hipStream_t st, bool& taken) {
     hipLaunchKernelGGL((gemm_pt_kernel<T>), dim3((unsigned)grid), dim3(512), PT_LDS_BYTES, st, d, tiles_n, (int)ntiles, skew);
     taken = true;
     ++g_pt_launches;
-    return lwdetr_check_launch();
+    return lwdetr_gemm_path_done(GP_PT, lwdetr_check_launch());
 }
 
 }  // namespace

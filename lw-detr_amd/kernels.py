@@ -120,20 +120,40 @@ class GemmOp:
         self._keep = (A, A2, W, segs, ws) + tuple(keep)
         self._fn = _nat.lib().lwdetr_gemm
         self._ref = C.byref(d)
-        # few rows (one or two images), one plain LINEAR segment: the few-row kernel on a fragment-major copy of W (made here, once per plan)
-        sg0 = segs[0]
-        if (type(self) is GemmOp and len(segs) == 1 and A2 is None and nsplit < 2 and sg0.mode == OUT_LINEAR and not sg0.rowmask and not sg0.ln_stats
-                and sg0.res_mod == 0 and N_ % 16 == 0 and K % 32 == 0 and a_mode == A_PLAIN and d.lda % 8 == 0 and sg0.ldo % 4 == 0
+        self._fallback = None
+        # few rows (one or two images), one plain LINEAR segment: the few-row kernel on a fragment-major copy of W (made here, once per plan) -
+        # on the descriptors lwdetr_gemm_few itself takes (few_entry_takes); the row-major descriptor stays the fallback for anything it refuses
+        if (type(self) is GemmOp and len(segs) == 1 and A2 is None and nsplit < 2 and a_mode == A_PLAIN and few_entry_takes(d)
                 and gemm_few_supported(A.dtype, M, A_PLAIN, 0, K)):
             Wf = pack_frag16(W)
-            d.W = _ptr(Wf)
-            self._keep = self._keep + (Wf,)
-            self._fn = _nat.lib().lwdetr_gemm_few
+            df = GemmDesc.from_buffer_copy(d)
+            df.W = _ptr(Wf)
+            self._keep = self._keep + (Wf, df)
+            self._fallback = (self._fn, self._ref)           # (lwdetr_gemm on the row-major descriptor)
+            # self.desc is the descriptor launched first (fragment-major W); the row-major one behind _fallback is a separate copy - code that
+            # patches self.desc in place after construction must patch both (none does: engine.py patches only PATCH16 ops, never routed here)
+            self.desc, self._fn, self._ref = df, _nat.lib().lwdetr_gemm_few, C.byref(df)
 
     def __call__(self, stream=None):
-        rc = self._fn(self._ref, self.dtype, stream if stream is not None else _nat.stream_ptr())
+        st = stream if stream is not None else _nat.stream_ptr()
+        rc = self._fn(self._ref, self.dtype, st)
+        if rc == _nat.ERR_UNSUPPORTED and self._fallback is not None:
+            fn, ref = self._fallback
+            rc = fn(ref, self.dtype, st)
         if rc:
             _nat.check(rc, f"gemm M={self.desc.M} N={self.desc.N} K={self.desc.K} a_mode={self.desc.a_mode}")
+
+
+def few_entry_takes(d) -> bool:
+    """The host-side conditions of lwdetr_gemm_few (few.hip) on a descriptor with PLAIN A: one LINEAR segment over all N columns without row mask,
+    periodic residual or folded LayerNorm; K % 32, N % 16; 16-bit A (lda % 8, 16-byte aligned); out / residual / second destination in 8-byte
+    runs of 4 (strides % 4, 8-byte aligned); bias / gamma 16-byte aligned; a known activation."""
+    g = d.seg[0]
+    al = lambda p, a: (p or 0) % a == 0
+    return (d.nseg == 1 and not d.A2 and d.a_mode == A_PLAIN and g.mode == OUT_LINEAR and not g.rowmask and not g.ln_stats and g.res_mod <= 0
+            and g.n_begin == 0 and g.n_end == d.N and d.N % 16 == 0 and d.K % 32 == 0 and d.lda % 8 == 0 and al(d.A, 16)
+            and g.ldo % 4 == 0 and al(g.out, 8) and (not g.res or (g.ldres % 4 == 0 and al(g.res, 8)))
+            and (not g.out2 or (g.ld2 % 4 == 0 and al(g.out2, 8))) and al(g.bias, 16) and al(g.gamma, 16) and ACT_NONE <= g.act <= ACT_SILU)
 
 
 GEMM_FEW_MAX_ROWS = 3200        # one or two 640 x 640 images (see gemm_few_supported)

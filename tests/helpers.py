@@ -1,4 +1,5 @@
-"""Shared test utilities: golden loading, deterministic weights, key->shape tables."""
+"""Shared test utilities: golden loading, deterministic weights, key->shape tables, the GEMM launch-path record."""
+import contextlib
 import os
 
 import numpy as np
@@ -162,3 +163,22 @@ def box_iou_xyxy(a, b):
     aa = np.clip(a[:, 2:] - a[:, :2], 0, None).prod(-1)
     ab = np.clip(b[:, 2:] - b[:, :2], 0, None).prod(-1)
     return inter / np.maximum(aa[:, None] + ab[None, :] - inter, 1e-9)
+
+
+@contextlib.contextmanager
+def served_by(family, launches=1):
+    """Asserts that the lwdetr_gemm / lwdetr_gemm_few launches inside the block went to exactly the kernel family `family` (a name of
+    lwdetr_gemm_path_name: "gemm_dma_64x64_d3", "gemm_big_256_kb64", "gemm_pt", "gemm_few_conv_kch6", ...), `launches` times (None: at least
+    once), and to no other."""
+    import torch
+    from lwdetr_amd import _native
+    before = _native.gemm_path_counts()
+    assert family in before, f"unknown GEMM kernel family {family!r}: {sorted(before)}"
+    yield
+    torch.cuda.synchronize()
+    after = _native.gemm_path_counts()
+    delta = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+    if launches is None:
+        assert set(delta) == {family}, f"expected launches of {family} only, the launches went to {delta}"
+    else:
+        assert delta == {family: launches}, f"expected {launches} launch(es) of {family}, the launches went to {delta}"

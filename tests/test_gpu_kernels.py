@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import served_by
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
@@ -61,7 +63,8 @@ def test_gemm_qkv_head_layouts(dtype, hd, b, tp):
     _check_qkv_layouts(dtype, hd, b, tp)
 
 
-def _check_qkv_layouts(dtype, hd, b, tp):
+def _check_qkv_layouts(dtype, hd, b, tp, family=None):
+    import contextlib
     from lwdetr_amd import kernels as K
     heads = 12
     c = heads * hd
@@ -71,10 +74,11 @@ def _check_qkv_layouts(dtype, hd, b, tp):
     q = torch.zeros(b, heads, tp, hd, dtype=dtype, device=_dev())
     k = torch.zeros_like(q)
     vt = torch.zeros(b, heads, hd, tp, dtype=dtype, device=_dev())
-    K.GemmOp(x, w, b * tp, 3 * c, c, [
-        K.seg(q, 0, c, mode=K.OUT_HEADS, bias=qb, scale=0.37, p0=tp, p1=hd, p2=heads),
-        K.seg(k, c, 2 * c, mode=K.OUT_HEADS, p0=tp, p1=hd, p2=heads),
-        K.seg(vt, 2 * c, 3 * c, mode=K.OUT_HEADS_T, bias=vb, p0=tp, p1=hd, p2=heads)])()
+    with served_by(family) if family else contextlib.nullcontext():
+        K.GemmOp(x, w, b * tp, 3 * c, c, [
+            K.seg(q, 0, c, mode=K.OUT_HEADS, bias=qb, scale=0.37, p0=tp, p1=hd, p2=heads),
+            K.seg(k, c, 2 * c, mode=K.OUT_HEADS, p0=tp, p1=hd, p2=heads),
+            K.seg(vt, 2 * c, 3 * c, mode=K.OUT_HEADS_T, bias=vb, p0=tp, p1=hd, p2=heads)])()
     y = x.float() @ w.float().t()
     sp = lambda t: t.reshape(b, tp, heads, hd).permute(0, 2, 1, 3)
     assert _relerr(q, sp((y[:, :c] + qb) * 0.37)) < TOL[dtype]
@@ -158,8 +162,13 @@ def test_gemm_few_rows_conv3x3_and_plain(dtype, b, hp, wp, cin, cout, stride):
     outs = []
     for cls, wt in ((K.GemmFewOp, K.pack_frag16(wk)), (K.GemmOp, wk)):
         out = torch.full((m, cout + 8), 7.0, dtype=dtype, device=_dev())
-        cls(x.reshape(-1, ctot), wt, m, cout, 9 * cin, [K.seg(out, 0, cout, ldo=cout + 8, bias=bias, act=K.ACT_SILU)], lda=ctot, a_mode=K.A_CONV3x3,
-            a_tok=K.tok_layout(False, hp, wp, 0), conv_cin=cin, conv_stride=stride, a_col0=col0, conv_hout=ho, conv_wout=wo)()
+        op = cls(x.reshape(-1, ctot), wt, m, cout, 9 * cin, [K.seg(out, 0, cout, ldo=cout + 8, bias=bias, act=K.ACT_SILU)], lda=ctot, a_mode=K.A_CONV3x3,
+                 a_tok=K.tok_layout(False, hp, wp, 0), conv_cin=cin, conv_stride=stride, a_col0=col0, conv_hout=ho, conv_wout=wo)
+        if cls is K.GemmFewOp:
+            with served_by("gemm_few_conv_kch6" if cin == 192 else "gemm_few_conv_kch4"):
+                op()
+        else:
+            op()
         outs.append(out)
     xin = x[..., col0:col0 + cin].float().permute(0, 3, 1, 2)
     ref = F.silu(F.conv2d(xin, w.float(), bias, stride=stride, padding=1)).permute(0, 2, 3, 1).reshape(-1, cout)
@@ -172,8 +181,9 @@ def test_gemm_few_rows_conv3x3_and_plain(dtype, b, hp, wp, cin, cout, stride):
     wl = _rand(n, k, dtype=dtype, scale=k ** -0.5, seed=5)
     gamma, res = _rand(n, seed=6), _rand(m, n, dtype=dtype, seed=7)
     o1, taps = torch.zeros(m, n, dtype=dtype, device=_dev()), torch.zeros(m, 2 * n, dtype=dtype, device=_dev())
-    K.GemmFewOp(a, K.pack_frag16(wl), m, n, k, [K.seg(o1, 0, n, ldo=n, bias=bias, act=K.ACT_GELU, scale=0.5, gamma=gamma, res=res, ldres=n,
-                                                   out2=taps[:, n:], ld2=2 * n)])()
+    with served_by("gemm_few_plain"):
+        K.GemmFewOp(a, K.pack_frag16(wl), m, n, k, [K.seg(o1, 0, n, ldo=n, bias=bias, act=K.ACT_GELU, scale=0.5, gamma=gamma, res=res, ldres=n,
+                                                       out2=taps[:, n:], ld2=2 * n)])()
     refp = res.float() + gamma * 0.5 * F.gelu(a.float() @ wl.float().t() + bias)
     assert _relerr(o1, refp) < TOL[dtype] and torch.equal(taps[:, n:], o1) and bool((taps[:, :n] == 0).all())
 
@@ -197,10 +207,14 @@ def test_gemm_conv3x3_large_tile(dtype, stride, winmajor, cout, wg2, big_gemm, m
     a = _to_winmajor(x, twp) if winmajor else x.reshape(-1, ctot)
     ho, wo = (hp - 1) // stride + 1, (wp - 1) // stride + 1
     out = torch.zeros(b * ho * wo, cout, dtype=dtype, device=_dev())
-    K.GemmOp(a.contiguous(), w.permute(0, 2, 3, 1).reshape(cout, -1).contiguous(), b * ho * wo, cout, 9 * cin,
-             [K.seg(out, 0, cout, ldo=cout, bias=bias, act=K.ACT_SILU)], lda=ctot, a_mode=K.A_CONV3x3,
-             a_tok=K.tok_layout(winmajor, hp, wp, twp), conv_cin=cin, conv_stride=stride, a_col0=col0, conv_hout=ho,
-             conv_wout=wo)()
+    # column tile: 192 for N <= 192, 256 for N % 256 == 0, else 128 (gemm.hip: try_launch_big); wg2 = 2: the 4-wave form where it exists
+    bn = 192 if cout <= 192 else (256 if cout % 256 == 0 else 128)
+    family = f"gemm_big4_{bn}" if wg2 == "2" and bn != 128 else f"gemm_big_{bn}_kb64"
+    with served_by(family):
+        K.GemmOp(a.contiguous(), w.permute(0, 2, 3, 1).reshape(cout, -1).contiguous(), b * ho * wo, cout, 9 * cin,
+                 [K.seg(out, 0, cout, ldo=cout, bias=bias, act=K.ACT_SILU)], lda=ctot, a_mode=K.A_CONV3x3,
+                 a_tok=K.tok_layout(winmajor, hp, wp, twp), conv_cin=cin, conv_stride=stride, a_col0=col0, conv_hout=ho,
+                 conv_wout=wo)()
     xin = x[..., col0:col0 + cin].float().permute(0, 3, 1, 2)
     ref = F.silu(F.conv2d(xin, w.float(), bias, stride=stride, padding=1)).permute(0, 2, 3, 1).reshape(-1, cout)
     assert _relerr(out, ref) < TOL[dtype]
@@ -221,10 +235,15 @@ def test_gemm_conv3x3_patch_resident(dtype, b, hp, wp, c, monkeypatch, knobs):
     for patch in ("2", "0"):
         knobs.set("CONV_PATCH", patch)
         out = torch.full((b * hp * wp, ctot), 3.0, dtype=dtype, device=_dev())
-        K.GemmOp(x.reshape(-1, ctot), w.permute(0, 2, 3, 1).reshape(c, -1).contiguous(), b * hp * wp, c, 9 * c,
-                 [K.seg(out[:, ocol:], 0, c, ldo=ctot, bias=bias, act=K.ACT_SILU)], lda=ctot, a_mode=K.A_CONV3x3,
-                 a_tok=K.tok_layout(False, hp, wp, 0), conv_cin=c, conv_stride=1, a_col0=col0, conv_hout=hp, conv_wout=wp,
-                 keep=(out,))()
+        op = K.GemmOp(x.reshape(-1, ctot), w.permute(0, 2, 3, 1).reshape(c, -1).contiguous(), b * hp * wp, c, 9 * c,
+                      [K.seg(out[:, ocol:], 0, c, ldo=ctot, bias=bias, act=K.ACT_SILU)], lda=ctot, a_mode=K.A_CONV3x3,
+                      a_tok=K.tok_layout(False, hp, wp, 0), conv_cin=c, conv_stride=1, a_col0=col0, conv_hout=hp, conv_wout=wp,
+                      keep=(out,))
+        if patch == "2":
+            with served_by(f"conv3x3_patch_{c}"):
+                op()
+        else:
+            op()
         torch.cuda.synchronize()
         assert bool((out[:, :ocol] == 3.0).all()) and bool((out[:, ocol + c:] == 3.0).all())        # nothing outside the segment
         outs.append(out[:, ocol:ocol + c].clone())
@@ -422,22 +441,27 @@ def big_gemm():
                                        # round 5: the 4-wave / 128-row form (two workgroups per CU; column tiles 256 and 192), ragged M / N tails
                                        ((1000, 768, 768), 128), ((4099, 256, 3072), 128), ((2000, 2304, 768), 128), ((777, 192, 384), 128),
                                        ((129, 1100, 448), 128), ((5000, 3072, 768), 128)])
-def test_gemm_large_tile_kernel(dtype, mnk, depth):
+def test_gemm_large_tile_kernel(dtype, mnk, depth, monkeypatch):
     """gemm_big_kernel (256 x 256 / 256 x 128 tiles, 32x32x16 MFMA, DMA ring of 32- and 64-deep stages; depth 128 = the 4-wave
-    128 x 256 / 128 x 192 form) vs torch: bias, GELU, LayerScale + residual epilogue; ragged M and N tails."""
+    128 x 256 / 128 x 192 form) vs torch: bias, GELU, LayerScale + residual epilogue; ragged M and N tails. Both launches are pinned to
+    the large-tile family (GemmOp's few-row route is off: at M <= 640 it would take these launches)."""
     from lwdetr_amd import _native, kernels as K
     if depth == 128:
         _need_experiments()
+    monkeypatch.setenv("LWDETR_GEMM_FEW", "0")
     m, n, k = mnk
     x = _rand(m, k, dtype=dtype, seed=1)
     w = _rand(n, k, dtype=dtype, scale=k ** -0.5, seed=2)
     bias = _rand(n, dtype=torch.float32, seed=3)
     gamma = _rand(n, dtype=torch.float32, seed=4)
     res = _rand(m, n, dtype=dtype, seed=5)
+    bn = 256 if n % 256 == 0 or n > 512 else (192 if n <= 192 else 128)
+    family = f"gemm_big4_{bn}" if depth == 128 else f"gemm_big_{bn}_kb{32 if depth == 32 else 64}"
     _native.lib().lwdetr_gemm_tuning(depth)
     try:
-        out = K.linear(x, w, bias, act=K.ACT_GELU, res=res, gamma=gamma)
-        plain = K.linear(x, w, bias)
+        with served_by(family, launches=2):
+            out = K.linear(x, w, bias, act=K.ACT_GELU, res=res, gamma=gamma)
+            plain = K.linear(x, w, bias)
     finally:
         _native.lib().lwdetr_gemm_tuning(-1)
     base = K.linear(x, w, bias)                              # default kernel choice (64 x 64 tiles at these sizes)
@@ -465,12 +489,14 @@ def _pt_vs_big(run):
     try:
         lib.lwdetr_gemm_pt_tuning(2)
         n0 = lib.lwdetr_gemm_pt_count()
-        a = run()
+        with served_by("gemm_pt", launches=None):
+            a = run()
         torch.cuda.synchronize()
         assert lib.lwdetr_gemm_pt_count() > n0, "the persistent kernel refused a shape this test is meant to run on it"
         lib.lwdetr_gemm_pt_tuning(0)
         n1 = lib.lwdetr_gemm_pt_count()
-        b = run()
+        with served_by("gemm_big_256_kb64", launches=None):          # every shape here has whole 256-column segments
+            b = run()
         torch.cuda.synchronize()
         assert lib.lwdetr_gemm_pt_count() == n1
     finally:
@@ -563,8 +589,11 @@ def test_gemm_large_tile_kernel_head_layouts(dtype, hd, wg2, big_gemm, monkeypat
     if wg2 == "2":
         _need_experiments()
     knobs.set("GEMM_BIG_2WG", wg2)
-    _check_qkv_layouts(dtype, hd, 4, 1600)
-    _check_qkv_layouts(dtype, hd, 1, 1000)          # ragged last row tile (1000 = 7 x 128 + 104)
+    # hd 64: N = 2304, column tile 256; hd 32: segment boundaries at 384 -> 128; hd 16: boundaries at 192 fit no column tile of the kernel -
+    # the launch stays on the 64 x 64 ring kernel (pinned, so that a change of that choice shows)
+    family = {64: "gemm_big4_256" if wg2 == "2" else "gemm_big_256_kb64", 32: "gemm_big_128_kb64", 16: "gemm_dma_64x64_d3"}[hd]
+    _check_qkv_layouts(dtype, hd, 4, 1600, family)
+    _check_qkv_layouts(dtype, hd, 1, 1000, family)          # ragged last row tile (1000 = 7 x 128 + 104)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
@@ -600,10 +629,11 @@ def test_gemm_with_layernorm_folded_in(dtype, m, c, mode):
         if m % 4 == 0:
             q = torch.zeros(1, heads, tp, hd, dtype=dtype, device=_dev()); k = torch.zeros_like(q)
             vt = torch.zeros(1, heads, hd, tp, dtype=dtype, device=_dev())
-            K.GemmOp(x, wq_, m, 3 * c, c, [
-                K.seg(q, 0, c, mode=K.OUT_HEADS, bias=bq_[:c], scale=0.37, p0=tp, p1=hd, p2=heads, ln_stats=stats, ln_colsum=cs_[:c]),
-                K.seg(k, c, 2 * c, mode=K.OUT_HEADS, bias=bq_[c:2 * c], p0=tp, p1=hd, p2=heads, ln_stats=stats, ln_colsum=cs_[c:2 * c]),
-                K.seg(vt, 2 * c, 3 * c, mode=K.OUT_HEADS_T, bias=bq_[2 * c:], p0=tp, p1=hd, p2=heads, ln_stats=stats, ln_colsum=cs_[2 * c:])])()
+            with served_by("gemm_big_ln"):
+                K.GemmOp(x, wq_, m, 3 * c, c, [
+                    K.seg(q, 0, c, mode=K.OUT_HEADS, bias=bq_[:c], scale=0.37, p0=tp, p1=hd, p2=heads, ln_stats=stats, ln_colsum=cs_[:c]),
+                    K.seg(k, c, 2 * c, mode=K.OUT_HEADS, bias=bq_[c:2 * c], p0=tp, p1=hd, p2=heads, ln_stats=stats, ln_colsum=cs_[c:2 * c]),
+                    K.seg(vt, 2 * c, 3 * c, mode=K.OUT_HEADS_T, bias=bq_[2 * c:], p0=tp, p1=hd, p2=heads, ln_stats=stats, ln_colsum=cs_[2 * c:])])()
             y = ln @ wqkv.t() + bqkv
             tol = TOL[dtype] * 2
             assert _relerr(q, sp(y[:, :c]) * 0.37) < tol and _relerr(k, sp(y[:, c:2 * c])) < tol
@@ -611,7 +641,8 @@ def test_gemm_with_layernorm_folded_in(dtype, m, c, mode):
         # fc1 + GELU, against the fp32 formulation and against the two launches it replaces
         w1_, cs1_, b1_ = K.fold_layernorm(w1, b1, lw, lb, dtype)
         hid = torch.zeros(m, 4 * c, dtype=dtype, device=_dev())
-        K.GemmOp(x, w1_, m, 4 * c, c, [K.seg(hid, 0, 4 * c, ldo=4 * c, bias=b1_, act=K.ACT_GELU, ln_stats=stats, ln_colsum=cs1_)])()
+        with served_by("gemm_big_ln"):
+            K.GemmOp(x, w1_, m, 4 * c, c, [K.seg(hid, 0, 4 * c, ldo=4 * c, bias=b1_, act=K.ACT_GELU, ln_stats=stats, ln_colsum=cs1_)])()
         ref = F.gelu(ln @ w1.t() + b1)
         two = K.linear(K.layernorm(x, lw, lb, 1e-6), w1.to(dtype), b1, act=K.ACT_GELU)
         e_new, e_old = _relerr(hid, ref), _relerr(two, ref)

@@ -184,3 +184,201 @@ def test_no_lds_read_is_outstanding_at_any_barrier_of_the_library():
                 allowed = 8 if "enc_chain_kernel" in name else 0
                 assert reads + (n or 0) <= allowed, (os.path.basename(obj), name, b, reads, n)
     assert seen > 500, seen
+
+
+# ---- gemm_pt.hip: the `s_waitcnt vmcnt(16)` shortcut of a tile's first k-step -----------------------------------------------------------
+# vmcnt retires in order: waiting for at most 16 outstanding vector-memory operations means "every ring piece has landed" only while the
+# previous tile's epilogue issued its stores AFTER the ring's newest global_load_lds and no flat_* operation (which may retire out of order,
+# MI355X_MICROARCH vmcnt section) sits in between. The check walks the control-flow graph of the built kernel BACKWARD from each shortcut
+# wait (the vmcnt(16) that the stage barrier follows; the compiler's own vmcnt(16) inside the epilogue are not it) until a global_load_lds
+# ends the path, and requires: no flat_* on any such path; on every path that ends at a ring piece issued inside the tile loop (a strongly
+# connected component), an epilogue store; paths that end outside every cycle start at the prologue (first tile: `stores_behind` is still
+# false there, the vmcnt(0) branch runs). What the walk cannot count is the 16: the epilogue stores in `#pragma unroll 1` loops and under
+# run-time conditions (a ragged tile stores fewer rows and leaves `stores_behind` false; s_cbranch_execz skips, not followed here, are taken
+# only with no lane active), so a static path holds as few as one store instruction; that part rests on the source (`stores_behind = ma == m0`, full tiles only), which the test reads as well.
+def _cfg(lines):
+    """Instructions of one disassembled function -> (addresses, mnemonics, successor lists). Fails closed on a jump it cannot resolve."""
+    import re
+    addr, mn, text, tgt = [], [], [], []
+    for ln in lines:
+        m = re.match(r"\s*(\S+)(.*?)//\s*([0-9A-Fa-f]+):[^<]*(?:<\w+\+0x([0-9a-f]+)>)?", ln)
+        if not m:
+            continue
+        mn.append(m.group(1)); text.append(m.group(1) + m.group(2)); addr.append(int(m.group(3), 16))
+        tgt.append(int(m.group(4), 16) if m.group(4) else None)
+    base = addr[0]
+    at = {a: i for i, a in enumerate(addr)}
+    succ = []
+    for i, op in enumerate(mn):
+        nxt = [i + 1] if i + 1 < len(mn) else []
+        if op == "s_endpgm":
+            succ.append([])
+        elif op == "s_branch":
+            succ.append([at[base + tgt[i]]])
+        elif op.startswith("s_cbranch"):
+            succ.append([at[base + tgt[i]]] + nxt)
+        elif op == "s_setpc_b64":
+            # long jump: s_getpc_b64 s[a:b]; s_add_u32 sa, sa, lit; s_addc_u32 sb, sb, hi; s_setpc_b64 s[a:b]
+            j = i - 1
+            while j >= 0 and mn[j] != "s_getpc_b64":
+                j -= 1
+            assert i - j <= 4 and j >= 0, f"unresolved s_setpc_b64 at {addr[i]:#x}: {text[i]}"
+            lo = re.search(r"s_add_u32 \w+, \w+, (0x[0-9a-f]+|-?\d+)", " ".join(text[j:i]))
+            hi = re.search(r"s_addc_u32 \w+, \w+, (0x[0-9a-f]+|-?\d+)", " ".join(text[j:i]))
+            assert lo and hi, f"unresolved s_setpc_b64 at {addr[i]:#x}"
+            off = (int(lo.group(1), 0) & 0xffffffff) | ((int(hi.group(1), 0) & 0xffffffff) << 32)
+            off = off - (1 << 64) if off >> 63 else off
+            succ.append([at[addr[j] + 4 + off]])
+        else:
+            succ.append(nxt)
+    return addr, mn, succ
+
+
+def _in_cycle(succ):
+    """Nodes that lie on a cycle (iterative Tarjan)."""
+    n = len(succ)
+    index, low, on, stack, out = [-1] * n, [0] * n, [False] * n, [], [False] * n
+    counter = 0
+    for root in range(n):
+        if index[root] >= 0:
+            continue
+        work = [(root, 0)]
+        while work:
+            v, k = work.pop()
+            if k == 0:
+                index[v] = low[v] = counter; counter += 1
+                stack.append(v); on[v] = True
+            if k < len(succ[v]):
+                work.append((v, k + 1))
+                w = succ[v][k]
+                if index[w] < 0:
+                    work.append((w, 0))
+                elif on[w]:
+                    low[v] = min(low[v], index[w])
+                continue
+            for w in succ[v]:
+                if on[w] and index[w] > index[v]:
+                    low[v] = min(low[v], low[w])
+            if low[v] == index[v]:
+                comp = []
+                while True:
+                    w = stack.pop(); on[w] = False; comp.append(w)
+                    if w == v:
+                        break
+                if len(comp) > 1 or v in succ[v]:
+                    for w in comp:
+                        out[w] = True
+    return out
+
+
+def shortcut_waits(lines):
+    """For every shortcut `s_waitcnt vmcnt(16)` of one function: (address, fewest stores on a backward path to a ring piece issued inside the
+    tile loop, flat_* seen on any backward path, number of paths that end at a ring piece outside every cycle, fewest stores on those)."""
+    import re
+    from collections import deque
+    addr, mn, succ = _cfg(lines)
+    txt = [ln.split("//")[0].strip() for ln in lines if re.search(r"//\s*[0-9A-Fa-f]+:", ln)]
+    assert len(txt) == len(mn)
+    pred = [[] for _ in mn]
+    for i, s_ in enumerate(succ):
+        for k, j in enumerate(s_):
+            if mn[i] == "s_cbranch_execz" and k == 0:
+                continue        # taken only when no lane is active: every lane of a full tile's epilogue owns outputs
+            pred[j].append(i)
+    cyc = _in_cycle(succ)
+    sites = []
+    for i, t in enumerate(txt):
+        if t == "s_waitcnt vmcnt(16)":
+            j = i + 1
+            while j < len(txt) - 1 and not txt[j].startswith(("s_barrier", "s_waitcnt", "global_", "buffer_", "flat_", "ds_")):
+                j += 1
+            if txt[j] == "s_barrier":
+                sites.append(i)
+    res = []
+    for w in sites:
+        dist = {w: 0}
+        dq = deque([w])
+        loop_min, flat, pro, pro_min = None, False, 0, None
+        while dq:
+            v = dq.popleft()
+            for p in pred[v]:
+                d = dist[v] + (1 if mn[p].startswith("global_store") else 0)
+                if p in dist and dist[p] <= d:
+                    continue
+                dist[p] = d
+                if mn[p].startswith("global_load_lds"):           # the ring's newest piece on this path: the path ends here
+                    if cyc[p]:
+                        loop_min = d if loop_min is None else min(loop_min, d)
+                    else:
+                        pro, pro_min = pro + 1, d if pro_min is None else min(pro_min, d)
+                    continue
+                if mn[p].startswith("flat_"):
+                    flat = True
+                if d > dist[v]:
+                    dq.append(p)
+                else:
+                    dq.appendleft(p)
+        res.append((addr[w], loop_min, flat, pro, pro_min))
+    return res
+
+
+def _pt_functions(dis):
+    import re
+    funcs, cur = {}, None
+    for ln in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(\w+)>:", ln)
+        if m:
+            cur = funcs.setdefault(m.group(1), []) if "gemm_pt_kernel" in m.group(1) else None
+        elif cur is not None and "//" in ln:
+            cur.append(ln)
+    return funcs
+
+
+def _check_pt_vmcnt16(dis):
+    funcs = _pt_functions(dis)
+    assert len(funcs) == 2, sorted(funcs)                   # f16 and bf16
+    for name, lines in funcs.items():
+        sites = shortcut_waits(lines)
+        assert len(sites) == 2, (name, "expected one shortcut wait per operand order (ROW / COL k-loop)", sites)
+        for a, loop_min, flat, pro, pro_min in sites:
+            assert not flat, (name, hex(a), "a flat_* operation between the ring's newest piece and vmcnt(16)")
+            assert loop_min is not None, (name, hex(a), "no path from a ring piece inside the tile loop")
+            assert loop_min >= 1, (name, hex(a), "a loop path with no epilogue store behind the ring's newest piece")
+            assert pro >= 1 and pro_min == 0, (name, hex(a), "the first-tile (prologue) paths are not where they were")
+
+
+def test_pt_vmcnt16_shortcut_paths():
+    src = open(os.path.join(ROOT, "lw-detr_amd", "csrc", "gemm_pt.hip")).read()
+    # the run-time half of the argument: the shortcut is taken only behind a full tile's epilogue (>= 16 stores per wave), never on the first tile
+    assert "bool stores_behind = false;" in src and "stores_behind = ma == m0;" in src
+    assert 'if (FIRST && stores_behind) asm volatile("s_waitcnt vmcnt(16)"' in src
+    _check_pt_vmcnt16(_pt_disassembly())
+
+
+def _pt_disassembly():
+    obj = os.path.join(ROOT, "lw-detr_amd", "csrc", "build", "gemm_pt.o")
+    if not os.path.exists(obj):
+        pytest.skip("library objects not built here")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_isa
+    return check_isa.device_disassembly(obj, "gfx950")
+
+
+def test_pt_vmcnt16_guard_flags_hand_edited_disassembly():
+    """The same check on edited copies of the disassembly (every edit keeps the instruction addresses): the epilogue stores renamed to an
+    opcode that is not a store, and a flat load in front of a shortcut wait - each one is refused; the unedited text passes."""
+    import re
+    dis = _pt_disassembly()
+    _check_pt_vmcnt16(dis)
+    with pytest.raises(AssertionError, match="no epilogue store"):
+        _check_pt_vmcnt16(re.sub(r"\tglobal_store_\w+ ", "\tv_nop ", dis))
+    ls = dis.splitlines()
+    i16 = next(i for i, ln in enumerate(ls) if ln.startswith("\ts_waitcnt vmcnt(16)") and
+               next(x for x in ls[i + 1:] if x.startswith("\ts_")).startswith(("\ts_barrier", "\ts_ashr", "\ts_mov", "\ts_add")))
+    j = i16 - 1
+    while ls[j].split()[0].startswith(("s_cbranch", "s_branch", "s_setpc", "s_getpc", "s_add", "s_endpgm", "s_waitcnt")):
+        j -= 1
+    edited = ls[:]
+    edited[j] = re.sub(r"^\t\S+[^/]*", "\tflat_load_dword v0, v[0:1] ", edited[j])
+    with pytest.raises(AssertionError, match="flat_"):
+        _check_pt_vmcnt16("\n".join(edited))
