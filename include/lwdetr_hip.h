@@ -134,7 +134,8 @@ int lwdetr_gemm_few(const lwdetr_gemm_desc* desc, int dtype, void* hip_stream);
 /* Row statistics of x (M, C) for the LayerNorm-folded GEMM: stats[m] = mean, stats[M + m] = 1 / sqrt(var + eps) (planar - interleaved pairs made
  * hipcc broadcast the high half of a register pair into packed-f32 epilogue arithmetic, the instruction form tools/check_isa.py refuses),
  * two-pass f32 on the stored values -
- * the arithmetic of lwdetr_layernorm without its output pass (half its HBM traffic). C % 8 == 0 (16-bit) / C % 4 == 0 (f32). */
+ * the arithmetic of lwdetr_layernorm without its output pass (half its HBM traffic). C % 8 == 0 (16-bit) / C % 4 == 0 (f32).
+ * LWDETR_ERR_BAD_ARG for ldx < C or an x that is not 16-byte aligned (the rows are read in 16-byte chunks). */
 int lwdetr_row_stats(const void* x, long ldx, long M, int C, float eps, float* stats, int dtype, void* hip_stream);
 /* Kernel selection override for tests / tuning (process-wide): big_mode -1 = default (environment LWDETR_GEMM_BIG, else
  * shape thresholds), 0 = never use the 256-row large-tile kernel, 2 = use it whenever the shape is legal for it,
@@ -188,7 +189,12 @@ void lwdetr_attention_tuning(int lds_mode);
 void lwdetr_attention_tuning_cfg(int cfg);
 
 /* ---- row LayerNorm: out[r,:] = (x[r,:]-mean)/sqrt(var+eps)*gamma+beta; biased variance; C % 4 == 0 ------------- */
-/* rows_per_batch / out_batch_stride / out_row_offset let the projector write straight into `memory` (B,S,d). */
+/* rows_per_batch / out_batch_rows / out_row_offset let the projector write straight into `memory` (B,S,d): input row b * rows_per_batch + r
+ * lands in output row b * out_batch_rows + out_row_offset + r (rows_per_batch <= 0: no remap).
+ * Refused with LWDETR_ERR_BAD_ARG before anything is launched (lwdetr_layernorm, _chain, lwdetr_ffn_finish): ldx < C, ldo < C, ldo2 < C;
+ * a remap with out_batch_rows < rows_per_batch, out_row_offset < 0 or out_row_offset + rows_per_batch > out_batch_rows (the slice
+ * would run into the next batch); x, out, out2 or partial not 16-byte aligned (rows move in 16-byte chunks; ld* must be whole chunks,
+ * C <= 2048 (16-bit) / 1024 (f32): LWDETR_ERR_UNSUPPORTED otherwise). */
 int lwdetr_layernorm(const void* x, long ldx, const float* gamma, const float* beta, void* out, long ldo, long M,
                      int C, float eps, long rows_per_batch, long out_batch_rows, long out_row_offset, int dtype,
                      void* hip_stream);
@@ -331,11 +337,14 @@ int lwdetr_vit_stem(const void* img, int B, int img_h, int img_w, int Hp, int Wp
 
 /* ---- fused glue of the two-stage selection / decoder set-up (reference models/transformer.py:236-276, :42-68, :352-355;
  * models/lwdetr.py:150-155, :168-170). idx (B,nq) int64 = two-stage top-k; props (B,S,4) f32 anchor proposals. ---- */
+/* om (B,S,d), enc_cls (B*S rows, row stride ldc >= ncls) -> om_sel (B,nq,d), logits_out (B,nq,ncls), props_sel (B,nq,4): pure copies of
+ * row b * S + idx[b,q]. LWDETR_ERR_BAD_ARG for B, S, d, nq or ncls <= 0 and for ldc < ncls. */
 int lwdetr_select_gather(const void* om, const void* enc_cls, long ldc, const float* props, const int64_t* idx,
                          void* om_sel, void* logits_out, float* props_sel, int B, int S, int d, int nq, int ncls,
                          int dtype, void* hip_stream);
 /* enc_delta (B*nq,4): bbox-MLP output of the selected rows; writes enc boxes (B,nq,4), decoder reference boxes ref_out
- * (B,nq,4) f32, the (y,x,w,h) sine embedding of ref * valid_ratio[level 0] (B*nq, 2d) and the broadcast queries (B*nq, d). */
+ * (B,nq,4) f32, the (y,x,w,h) sine embedding of ref * valid_ratio[level 0] (B*nq, 2d) and the broadcast queries (B*nq, d).
+ * valid_ratios (B,L,2) (x,y). LWDETR_ERR_BAD_ARG for B, nq, d or L <= 0 and for an odd d. */
 int lwdetr_decoder_inputs(const void* enc_delta, const float* props_sel, const float* refpoint, const float* valid_ratios,
                           int L, const void* query_feat, const float* dim_t, void* enc_boxes_out, float* ref_out,
                           void* sine_out, void* xdec_out, int B, int nq, int d, int dtype, void* hip_stream);
@@ -345,7 +354,8 @@ int lwdetr_box_reparam(const void* delta, const float* ref, long ref_rows, void*
  * user-visible pred_boxes / pred_logits of all decoder layers (models/lwdetr.py:150-173) in one launch. Input row
  * layer * ref_rows + k is written to output row layer * out_layer_rows + k (out_layer_rows >= ref_rows; 0 = ref_rows, i.e.
  * contiguous): a call that owns images [b0, b0 + B) of a (layers, B_total, nq, .) tensor passes the pointers of row b0 * nq and
- * out_layer_rows = B_total * nq. */
+ * out_layer_rows = B_total * nq. logits_out and logits_pad must NOT overlap (the kernel reads one and writes the other without ordering
+ * between threads): logits_out == logits_pad is refused with LWDETR_ERR_BAD_ARG, as are ncls <= 0, ldc < ncls, out_layer_rows < ref_rows. */
 int lwdetr_finalize_outputs(const void* delta, const float* ref, long ref_rows, void* coord_out, long R, const void* logits_pad,
                             long ldc, int ncls, void* logits_out, long out_layer_rows, int dtype, void* hip_stream);
 

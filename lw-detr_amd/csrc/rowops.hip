@@ -7,6 +7,9 @@ namespace {
 
 constexpr int LN_MAX_CHUNKS = 16;   // per lane: supports C <= 16 lanes * 16 chunks * EPC (2048 for 16-bit, 1024 for f32)
 
+// every row kernel below moves 16-byte chunks: base pointers must sit on a 16-byte boundary (the leading dimensions are whole chunks, launch_ln)
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // Optional chained second LayerNorm (gamma2 != nullptr): out2 = LN2(out) computed on the values just rounded to T, i.e.
 // bit-identical to a second launch reading `out` (decoder: norm3 followed by the shared decoder.norm, transformer.py:466-517,
 // :397-400) - one pass over the row instead of two launches.
@@ -134,6 +137,11 @@ int launch_ln(const void* x, long ldx, const float* gamma, const float* beta, vo
               const float* beta2 = nullptr, void* out2 = nullptr, long ldo2 = 0, float eps2 = 0.f,
               const float* part = nullptr, int nsplit = 0, const float* pbias = nullptr) {
     constexpr int EPC = 16 / (int)sizeof(T);
+    // refusals, all on the host before anything is launched: rows that overlap (ld < C), a row remap whose slice does not fit its batch,
+    // pointers the 16-byte accesses cannot take
+    if (ldx < C || ldo < C || (gamma2 && ldo2 < C)) return LWDETR_ERR_BAD_ARG;
+    if (rpb > 0 && (obr < rpb || oro < 0 || oro + rpb > obr)) return LWDETR_ERR_BAD_ARG;
+    if (!aligned16(x) || !aligned16(out) || (gamma2 && !aligned16(out2)) || (part && !aligned16(part))) return LWDETR_ERR_BAD_ARG;
     if (C % EPC != 0 || C / EPC > 16 * LN_MAX_CHUNKS || ldx % EPC != 0 || ldo % EPC != 0 || ldo2 % EPC != 0) return LWDETR_ERR_UNSUPPORTED;
     const long blocks = (M + 15) / 16;
     ProfScope ps(KID_LAYERNORM, 0.0, (gamma2 ? 3.0 : 2.0) * M * C * sizeof(T) + 4.0 * nsplit * M * C, st);
@@ -193,6 +201,7 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const T* __restrict__ x,
 template <typename T>
 int launch_row_stats(const void* x, long ldx, long M, int C, float eps, float* stats, hipStream_t st) {
     constexpr int EPC = 16 / (int)sizeof(T);
+    if (ldx < C || !aligned16(x)) return LWDETR_ERR_BAD_ARG;
     if (C % EPC != 0 || C / EPC > 16 * LN_MAX_CHUNKS || ldx % EPC != 0) return LWDETR_ERR_UNSUPPORTED;
     const long blocks = (M + 15) / 16;
     ProfScope ps(KID_LAYERNORM, 0.0, 1.0 * M * C * sizeof(T), st);
@@ -368,7 +377,8 @@ __global__ __launch_bounds__(256) void finalize_outputs_kernel(const T* __restri
 extern "C" int lwdetr_select_gather(const void* om, const void* enc_cls, long ldc, const float* props, const int64_t* idx,
                                     void* om_sel, void* logits_out, float* props_sel, int B, int S, int d, int nq, int ncls,
                                     int dtype, void* hip_stream) {
-    if (!om || !enc_cls || !props || !idx || !om_sel || !logits_out || !props_sel || B <= 0 || nq <= 0) return LWDETR_ERR_BAD_ARG;
+    if (!om || !enc_cls || !props || !idx || !om_sel || !logits_out || !props_sel || B <= 0 || nq <= 0 || S <= 0 ||
+        d <= 0 || ncls <= 0 || ldc < ncls) return LWDETR_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)hip_stream;
     ProfScope ps(KID_ELTWISE, 0.0, 2.0 * B * nq * (d + ncls) * 2, st);
     LWDETR_DISPATCH_T(dtype, hipLaunchKernelGGL((select_gather_kernel<TT>), dim3(B * nq), dim3(256), 0, st, (const TT*)om,
@@ -381,7 +391,7 @@ extern "C" int lwdetr_decoder_inputs(const void* enc_delta, const float* props_s
                                      int L, const void* query_feat, const float* dim_t, void* enc_boxes_out, float* ref_out,
                                      void* sine_out, void* xdec_out, int B, int nq, int d, int dtype, void* hip_stream) {
     if (!enc_delta || !props_sel || !refpoint || !valid_ratios || !query_feat || !dim_t || !enc_boxes_out || !ref_out ||
-        !sine_out || !xdec_out || B <= 0 || nq <= 0 || d % 2) return LWDETR_ERR_BAD_ARG;
+        !sine_out || !xdec_out || B <= 0 || nq <= 0 || d <= 0 || d % 2 || L <= 0) return LWDETR_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)hip_stream;
     ProfScope ps(KID_ELTWISE, 0.0, 3.0 * B * nq * d * 2, st);
     LWDETR_DISPATCH_T(dtype, hipLaunchKernelGGL((decoder_inputs_kernel<TT>), dim3(B * nq), dim3(256), 0, st, (const TT*)enc_delta,
@@ -404,6 +414,7 @@ extern "C" int lwdetr_finalize_outputs(const void* delta, const float* ref, long
                                        const void* logits_pad, long ldc, int ncls, void* logits_out, long out_layer_rows, int dtype,
                                        void* hip_stream) {
     if (!delta || !ref || !coord_out || !logits_pad || !logits_out || R < 0 || ref_rows <= 0 || ncls <= 0 || ldc < ncls) return LWDETR_ERR_BAD_ARG;
+    if (logits_out == logits_pad) return LWDETR_ERR_BAD_ARG;     // the kernel holds both __restrict__: they must not overlap
     if (out_layer_rows == 0) out_layer_rows = ref_rows;
     if (out_layer_rows < ref_rows) return LWDETR_ERR_BAD_ARG;
     if (R == 0) return LWDETR_OK;

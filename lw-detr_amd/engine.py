@@ -703,6 +703,7 @@ class ForwardPlan:
         self.enc_logits_sel, self.enc_boxes = z(B, nq, self.ncls), z(B, nq, 4)
         self.props_sel = f32(B, nq, 4)
         self.coord = z(nl, B, nq, 4)
+        self.cls_out = z(nl, B, nq, self.ncls)      # stands in for the call's logits tensor below: lwdetr_finalize_outputs refuses logits_out == logits_pad
         dim_t = torch.arange(d // 2, dtype=torch.float32, device=dev)
         self.dim_t = (10000 ** (2 * (dim_t // 2) / (d // 2))).contiguous()          # transformer.py:46-47
         ptr = lambda t_: t_.data_ptr()
@@ -717,7 +718,7 @@ class ForwardPlan:
             ptr(self.dim_t), ptr(self.enc_boxes), ptr(self.ref), ptr(self.sine), ptr(self.xdec), B, nq, d, code), keep=())
         self.op_finalize = K.RawOp("lwdetr_finalize_outputs", (
             ptr(self.delta), ptr(self.ref), B * nq, ptr(self.coord), nl * B * nq, ptr(self.logits), self.ldc, self.ncls,
-            ptr(self.logits), 0, code), keep=())     # args 3 (boxes), 8 (logits), 9 (rows per layer there): the call's output tensors
+            ptr(self.cls_out), 0, code), keep=())    # args 3 (boxes), 8 (logits), 9 (rows per layer there): the call's output tensors
 
     # ------------------------------------------------------------------------------- per-call host-side glue
     def _masks(self, mask):

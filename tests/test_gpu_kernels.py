@@ -716,14 +716,15 @@ def test_layernorm(dtype, c):
     g, b = _rand(c, seed=2), _rand(c, seed=3)
     out = K.layernorm(x, g, b, 1e-6)
     ref = F.layer_norm(x.float(), (c,), g, b, 1e-6)
-    assert (out.float() - ref).abs().max().item() < {torch.float32: 2e-5, torch.float16: 8e-3, torch.bfloat16: 6e-2}[dtype]
+    tol = {torch.float32: 2e-5, torch.float16: 8e-3, torch.bfloat16: 6e-2}[dtype]
+    assert (out.float() - ref).abs().max().item() < tol
     # batched row remap (projector LayerNorm writing into a level slice of memory)
     rows, s_total, off = 50, 64, 9
     xb = _rand(2 * rows, c, dtype=dtype, seed=4)
     ob = torch.zeros(2 * s_total, c, dtype=dtype, device=_dev())
     K.LayerNormOp(xb, g, b, ob, 2 * rows, c, 1e-6, rows_per_batch=rows, out_batch_rows=s_total, out_row_offset=off)()
     refb = F.layer_norm(xb.float(), (c,), g, b, 1e-6).reshape(2, rows, c)
-    assert (ob.reshape(2, s_total, c)[:, off:off + rows].float() - refb).abs().max().item() < 6e-2
+    assert (ob.reshape(2, s_total, c)[:, off:off + rows].float() - refb).abs().max().item() < tol
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
