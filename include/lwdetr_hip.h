@@ -127,9 +127,17 @@ int lwdetr_gemm(const lwdetr_gemm_desc* desc, int dtype, void* hip_stream);
 /* Few-row form (round 6; the single-image latency path): the same descriptor as lwdetr_gemm with W FRAGMENT-MAJOR - [N / 16][K / 32][16][32],
  * lwdetr_amd.kernels.pack_frag16 of the (N, K) matrix lwdetr_gemm takes. A workgroup owns 16 rows x 128 columns, a wave loads the MFMA fragments of a
  * third of the contraction straight from L2 before it multiplies them: no LDS ring, no barriers - the six 3x3 convolutions of the projector
- * (models/backbone/projector.py:101-132) at one 640 x 640 image 19.3 -> ~9 us each. Serves: 16-bit, M <= 8192, a_mode PLAIN or CONV3x3 (raster rows,
- * stride 1 | 2, Cin in {128, 192}), K % 32 == 0, N % 16 == 0, ONE LINEAR segment (bias, activation, scale, gamma, residual, second destination;
- * no row mask); LWDETR_ERR_UNSUPPORTED otherwise. Same arithmetic as lwdetr_gemm up to the f32 summation order of the contraction. */
+ * (models/backbone/projector.py:101-132) at one 640 x 640 image 19.3 -> ~9 us each. Serves: f16 / bf16 / f32, M <= 8192, a_mode PLAIN or CONV3x3 (raster
+ * rows, stride 1 | 2, Cin in {128, 192}, a_col0 % 8 == 0), K % 32 == 0, N % 16 == 0, ONE LINEAR segment over all N columns (bias, activation, scale,
+ * gamma, residual, second destination; no row mask, periodic residual, folded LayerNorm or A2); LWDETR_ERR_UNSUPPORTED otherwise, before any launch
+ * (nothing written, nothing counted); an unknown activation is LWDETR_ERR_BAD_ARG. Same arithmetic as lwdetr_gemm up to the f32 summation order of
+ * the contraction.
+ *   A 16 x 32 weight fragment is one contiguous KB in 16-bit and one contiguous 2 KB in f32. What the kernel accesses in wide pieces, per dtype:
+ *     16-bit: A and W 16-byte aligned, lda % 8 == 0 (16-byte loads of 8 values); out / res / out2 8-byte aligned, ldo / ldres / ld2 % 4 == 0.
+ *     f32   : A and W 16-byte aligned, lda % 4 == 0 (two 16-byte loads of 4 values); out / res / out2 16-byte aligned, ldo / ldres / ld2 % 4 == 0.
+ *     both  : bias / gamma 16-byte aligned.
+ *   The f32 form (dtype 0) contracts with the exact-f32 16x16x4 MFMA, f32 accumulation in k-chunk order, GELU in the erf form: the same arithmetic
+ *   as lwdetr_gemm in f32 up to summation order. The launch plan takes it only with LWDETR_GEMM_FEW_F32=1 (lwdetr_amd.kernels.gemm_few_supported). */
 int lwdetr_gemm_few(const lwdetr_gemm_desc* desc, int dtype, void* hip_stream);
 /* Row statistics of x (M, C) for the LayerNorm-folded GEMM: stats[m] = mean, stats[M + m] = 1 / sqrt(var + eps) (planar - interleaved pairs made
  * hipcc broadcast the high half of a register pair into packed-f32 epilogue arithmetic, the instruction form tools/check_isa.py refuses),

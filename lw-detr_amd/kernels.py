@@ -123,7 +123,7 @@ class GemmOp:
         self._fallback = None
         # few rows (one or two images), one plain LINEAR segment: the few-row kernel on a fragment-major copy of W (made here, once per plan) -
         # on the descriptors lwdetr_gemm_few itself takes (few_entry_takes); the row-major descriptor stays the fallback for anything it refuses
-        if (type(self) is GemmOp and len(segs) == 1 and A2 is None and nsplit < 2 and a_mode == A_PLAIN and few_entry_takes(d)
+        if (type(self) is GemmOp and len(segs) == 1 and A2 is None and nsplit < 2 and a_mode == A_PLAIN and few_entry_takes(d, A.dtype)
                 and gemm_few_supported(A.dtype, M, A_PLAIN, 0, K)):
             Wf = pack_frag16(W)
             df = GemmDesc.from_buffer_copy(d)
@@ -144,16 +144,21 @@ class GemmOp:
             _nat.check(rc, f"gemm M={self.desc.M} N={self.desc.N} K={self.desc.K} a_mode={self.desc.a_mode}")
 
 
-def few_entry_takes(d) -> bool:
-    """The host-side conditions of lwdetr_gemm_few (few.hip) on a descriptor with PLAIN A: one LINEAR segment over all N columns without row mask,
-    periodic residual or folded LayerNorm; K % 32, N % 16; 16-bit A (lda % 8, 16-byte aligned); out / residual / second destination in 8-byte
-    runs of 4 (strides % 4, 8-byte aligned); bias / gamma 16-byte aligned; a known activation."""
+def few_entry_takes(d, dtype) -> bool:
+    """The host-side conditions of lwdetr_gemm_few (few.hip) on a descriptor with PLAIN A and elements of ``dtype``: one LINEAR segment over all N
+    columns without row mask, periodic residual or folded LayerNorm; K % 32, N % 16, M <= 8192; A in 16-byte loads (16-byte aligned; lda % 8 in
+    16-bit, % 4 in f32) and W 16-byte aligned; out / residual / second destination in runs of 4 values (strides % 4; 8-byte aligned in 16-bit,
+    16-byte aligned in f32); bias / gamma 16-byte aligned; a known activation."""
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        return False
     g = d.seg[0]
+    a_run, o_al = (4, 16) if dtype == torch.float32 else (8, 8)
     al = lambda p, a: (p or 0) % a == 0
     return (d.nseg == 1 and not d.A2 and d.a_mode == A_PLAIN and g.mode == OUT_LINEAR and not g.rowmask and not g.ln_stats and g.res_mod <= 0
-            and g.n_begin == 0 and g.n_end == d.N and d.N % 16 == 0 and d.K % 32 == 0 and d.lda % 8 == 0 and al(d.A, 16)
-            and g.ldo % 4 == 0 and al(g.out, 8) and (not g.res or (g.ldres % 4 == 0 and al(g.res, 8)))
-            and (not g.out2 or (g.ld2 % 4 == 0 and al(g.out2, 8))) and al(g.bias, 16) and al(g.gamma, 16) and ACT_NONE <= g.act <= ACT_SILU)
+            and g.n_begin == 0 and g.n_end == d.N and d.N % 16 == 0 and d.K % 32 == 0 and 0 <= d.M <= 8192 and d.lda % a_run == 0
+            and al(d.A, 16) and al(d.W, 16)
+            and g.ldo % 4 == 0 and al(g.out, o_al) and (not g.res or (g.ldres % 4 == 0 and al(g.res, o_al)))
+            and (not g.out2 or (g.ld2 % 4 == 0 and al(g.out2, o_al))) and al(g.bias, 16) and al(g.gamma, 16) and ACT_NONE <= g.act <= ACT_SILU)
 
 
 GEMM_FEW_MAX_ROWS = 3200        # one or two 640 x 640 images (see gemm_few_supported)
@@ -163,9 +168,15 @@ def gemm_few_supported(dtype, M, a_mode=A_PLAIN, conv_cin=0, K=0) -> bool:
     """The launch-plan choice for lwdetr_gemm_few (the few-row kernel on fragment-major weights): the 3x3 convolutions of the projector at one or two
     images (19.3 -> 10.8 us each at one image), and plain single-segment Linear launches of a few hundred rows (the decoder's ref_point_head at one
     image: 11.5 -> 6.9, 8.5 -> 6.4 us; at 1600 rows the 64 x 64 ring kernel ties or wins - profiles/r6c_*). LWDETR_GEMM_FEW=2 takes every plain
-    launch it can (tuning), =0 keeps lwdetr_gemm everywhere (A/B runs)."""
+    launch it can (tuning), =0 keeps lwdetr_gemm everywhere (A/B runs). float32 follows the same shape rules, but only with LWDETR_GEMM_FEW_F32=1
+    (off by default; measured in profiles/r7a_few_row_gemm_f32.txt)."""
     mode = os.environ.get("LWDETR_GEMM_FEW", "1")
-    if mode == "0" or dtype not in (torch.float16, torch.bfloat16) or M > GEMM_FEW_MAX_ROWS:
+    if dtype == torch.float32:
+        if os.environ.get("LWDETR_GEMM_FEW_F32", "0") != "1":
+            return False
+    elif dtype not in (torch.float16, torch.bfloat16):
+        return False
+    if mode == "0" or M > GEMM_FEW_MAX_ROWS:
         return False
     if a_mode == A_CONV3x3:
         return conv_cin in (128, 192)

@@ -1,6 +1,6 @@
 """Single-image latency (forward + PostProcess as ONE HIP graph, host sync per image): p50 / p90 over 200 replays.
 
-    python tools/lat_bs1.py [--size small] [--res 640] [--dtype fp16] [--eager]
+    python tools/lat_bs1.py [--size small] [--res 640] [--dtype fp16|bf16|fp32] [--eager]
 Environment knobs of the kernels (LWDETR_*) apply as usual: the tool exists to A/B them on the latency path."""
 import argparse
 import os
@@ -15,14 +15,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="small")
     ap.add_argument("--res", type=int, default=640)
-    ap.add_argument("--dtype", default="fp16")
+    ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16", "fp32"])
     ap.add_argument("--eager", action="store_true")
     ap.add_argument("--n", type=int, default=200)
     a = ap.parse_args()
     import torch
     import lwdetr_amd
     from lwdetr_amd.synth import synth_images, synth_state_dict
-    T = {"fp16": torch.float16, "bf16": torch.bfloat16}[a.dtype]
+    T = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}[a.dtype]
     dev = torch.device("cuda:0")
     model, _, post = lwdetr_amd.build_model(lwdetr_amd.get_args(a.size))
     model.load_state_dict(synth_state_dict(model.state_dict(), seed=0))
