@@ -250,11 +250,16 @@ int lwdetr_mlp_fused(void* x, long ldx, const void* w1_folded, const float* b1_f
                      const float* gamma1, const void* wqkv_next, const float* bqkv_next, void* q_out, void* k_out,
                      void* vt_out, float qscale, int heads, int hd, int Tp, int dtype, void* hip_stream);
 
-/* The few-token form of lwdetr_mlp_fused with the attention projection (round 6; 16-bit, C = 192, M < 12800: the single-image latency path) on
+/* The few-token form of lwdetr_mlp_fused with the attention projection (round 6; C = 192, M < 12800: the single-image latency path) on
  * FRAGMENT-MAJOR weights: w1_frag, wp_frag, wqkv_frag_next = the w1_folded / wp / wqkv_next of lwdetr_mlp_fused re-laid out as
  * [R / 16][C / 32][16][32] (lwdetr_amd.kernels.pack_frag16), so that each 16 x 32 MFMA fragment the kernel loads straight from L2 is one
- * contiguous KB instead of 16 half lines. Everything else as lwdetr_mlp_fused (att required); results are bit-identical to it.
- * LWDETR_ERR_UNSUPPORTED outside (C, dtype, M) above. */
+ * contiguous KB (2 KB in float32) instead of 16 half lines. Everything else as lwdetr_mlp_fused (att required); in 16-bit the results are
+ * bit-identical to it.
+ * dtype 1 / 2 (f16 / bf16): ldx, ld2, ldatt multiples of 8 (LWDETR_ERR_BAD_ARG otherwise).
+ * dtype 0 (float32; the same structure on exact-f32 16x16x4 MFMAs, 16-token workgroups at every M; sums in another order than lwdetr_mlp_fused's
+ * f32 kernel, so equal to it only to rounding): ldx, ld2, ldatt multiples of 4, and x, att, out2, q_out, k_out, vt_out, w1_frag, wp_frag,
+ * wqkv_frag_next, w2_chunked, b1_folded, b2, bp, gamma1, gamma2, bqkv_next 16-byte aligned - LWDETR_ERR_UNSUPPORTED otherwise, before any launch.
+ * LWDETR_ERR_UNSUPPORTED outside (C, M) above and for any other dtype. */
 int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, const float* b1_folded, const void* w2_chunked, const float* b2,
                          const float* gamma2, void* out2, long ld2, float* stats_out, long M, int C, float eps, float eps_next,
                          const void* att, long ldatt, const void* wp_frag, const float* bp, const float* gamma1,

@@ -792,6 +792,238 @@ __global__ __launch_bounds__(NTHR, 1) void mlp_small_kernel(const MlpParams p) {
         }
     }
 }
+// ---- float32 form of the few-token kernel (lwdetr_vit_block_few with dtype 0; behind LWDETR_VIT_BLOCK_FEW_F32=1 in the launch plan): FRAG, TT = 1.
+// The structure above on f32 fragments: lane (l15, g) still holds the 8 values of k-slots 8 g .. 8 g + 7 of its row for BOTH operands - a weight fragment
+// is one contiguous 2 KB, read as two 16-byte loads - and Mma<float>::k32 contracts them as eight exact-f32 16x16x4 MFMAs (slice s pairs slot 8 g' + s of the
+// two operands over the four lane groups g': the same (lane group, slot) pairing as the 16x16x32 form, so pack_mlp_weights(proj=True) / pack_qkv_weights /
+// pack_frag16 serve f32 unchanged; tests/test_vit_block_few_f32_host.py follows the lanes). x1 stays f32 (the storage type): x1s is [16][C + 8] floats.
+// Registers: a fragment costs 8 VGPRs per lane, so the 16-bit plan (xf + all fc1 + all fc2 fragments of a chunk + acc2) would be 288 of a wave's 256. The 24
+// fragments of a hidden chunk (12 of fc1 in MFMA order, then 12 of fc2) are streamed in batches of MLP_SMALL_F32_NB through two register sets: batch b + 1 -
+// at the end of a chunk the first batch of the wave's next chunk - is requested before batch b multiplies (a batch of 4 is 32 dependent-free MFMAs per
+// accumulator pair, ~1000 clocks: more than an L2 round trip). The chained QKV keeps the 16-bit form: one feature tile (6 fragments) multiplies while the next is
+// in flight. Batch sizes built and their register counts: profiles/r7b_vit_block_few_f32.txt. TT = 2 is not built (xf and acc2 alone would be 192 registers).
+#ifndef MLP_SMALL_F32_NB
+#define MLP_SMALL_F32_NB 4
+#endif
+__device__ __forceinline__ f32x8 small_load8(const float* p) {       // two 16-byte loads: the entry checks 16-byte alignment, not 32
+    const f32x4 lo = *(const f32x4*)p, hi = *(const f32x4*)(p + 4);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+template <bool QKV>
+__device__ __forceinline__ void mlp_small_f32(const MlpParams& p) {
+    constexpr int C = 192, KC = C / 32, NT = C / 16, HID = 4 * C, NCH = HID / 32, X1_LD = C + 8;
+    constexpr int NB = MLP_SMALL_F32_NB, NF = 2 * KC + NT, NBAT = NF / NB;     // fragments per batch / per hidden chunk, batches per chunk
+    static_assert(12 % NB == 0 && NB < 12 && NBAT % 2 == 0, "a batch divides the 12 fragments of fc1 / fc2; a chunk starts in register set 0");
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* x1s = (float*)smem_raw;                                // [16][X1_LD]: x1, then the block's output rows
+    float* part = x1s + 16 * X1_LD;                               // [8 waves][6 tiles][64 lanes][4]
+    float* b1s = part + NW * 6 * 256;
+    float* bps = b1s + HID; float* bqs = bps + 2 * C; float* b2s = bqs + 3 * C;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, g = lane >> 4;
+    const long m0 = (long)blockIdx.x * 16;
+    float* __restrict__ X = (float*)p.x;
+    const int lfrag = l15 * 32 + g * 8;                           // this lane's 8 values inside a 16 x 32 fragment (512 floats)
+    const float* __restrict__ W1 = (const float*)p.w1 + lfrag;    // fragment (row tile rt, k-chunk kc) at (rt * KC + kc) * 512
+    const float* __restrict__ W2 = (const float*)p.w2p + lfrag;   // chunk-major: fragment (chunk hc, channel tile n) at (hc * NT + n) * 512
+    for (int i = tid; i < HID; i += NTHR) b1s[i] = p.b1[i];
+    for (int i = tid; i < C; i += NTHR) { bps[i] = p.bp[i]; bps[C + i] = p.gamma1[i]; b2s[i] = p.b2[i]; b2s[C + i] = p.gamma2[i]; }
+    if (QKV) for (int i = tid; i < 3 * C; i += NTHR) bqs[i] = p.bqkv[i];
+    const long mtok = m0 + l15;                                   // this lane's token row (clamped for loads)
+    const bool mok = mtok < p.M;
+    const long mrow = mok ? mtok : p.M - 1;
+    __syncthreads();                                              // biases visible
+
+    // ---- projection: wave pc < 6 -> channels 32 pc .. 32 pc + 31 of x1 = x + gamma1 * (att Wp^T + bp)
+    if (wave < KC) {
+        const int pc = wave;
+        const float* __restrict__ ATT = (const float*)p.att;
+        const float* __restrict__ WP = (const float*)p.wp + lfrag;
+        f32x8 af[KC], wa[2][KC];
+        f32x4 xr[2];
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) af[kc] = small_load8(ATT + mrow * p.ldatt + kc * 32 + g * 8);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) wa[h][kc] = small_load8(WP + (long)((pc * 2 + h) * KC + kc) * 512);
+            xr[h] = *(const f32x4*)(X + mrow * p.ldx + pc * 32 + h * 16 + g * 4);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int c0 = pc * 32 + h * 16 + g * 4;
+            const f32x4 bb = *(const f32x4*)(bps + c0), gg = *(const f32x4*)(bps + C + c0);
+            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) a = Mma<float>::k32(wa[h][kc], af[kc], a);
+            *(f32x4*)(x1s + l15 * X1_LD + c0) = xr[h] + gg * (a + bb);
+        }
+    }
+    __syncthreads();
+
+    // ---- every wave: the whole x1 tile as B fragments (k-slot order of the projection's accumulators), LayerNorm
+    f32x8 xf[KC];
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x4 v = *(const f32x4*)(x1s + l15 * X1_LD + kc * 32 + h * 16 + g * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xf[kc][h * 4 + e] = v[e];
+        }
+    {
+        float sm = 0.f;
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sm += xf[kc][e];
+        sm += __shfl_xor(sm, 16); sm += __shfl_xor(sm, 32);
+        const float mean = sm * (1.f / C);
+        float v = 0.f;
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float dl = xf[kc][e] - mean; v += dl * dl; }
+        v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+        const float rstd = 1.f / sqrtf(v * (1.f / C) + p.eps);
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xf[kc][e] = (xf[kc][e] - mean) * rstd;
+    }
+
+    // ---- hidden chunks wave, wave + 8, wave + 16: fragment f of a chunk is fc1's (k-chunk f / 2, row tile f % 2) for f < 12, fc2's channel tile f - 12 after
+    f32x4 acc2[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc2[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto load_batch = [&](int hc, int b, f32x8 (&dst)[NB]) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int f = b * NB + i;
+            dst[i] = f < 2 * KC ? small_load8(W1 + (long)((hc * 2 + (f & 1)) * KC + (f >> 1)) * 512)
+                                : small_load8(W2 + (long)(hc * NT + f - 2 * KC) * 512);
+        }
+    };
+    f32x8 fb[2][NB];
+    load_batch(wave, 0, fb[0]);
+#pragma unroll 1
+    for (int hc = wave; hc < NCH; hc += NW) {
+        const int hn = hc + NW < NCH ? hc + NW : hc;             // last chunk: a harmless reload
+        f32x4 acc1[2] = {*(const f32x4*)(b1s + hc * 32 + g * 4), *(const f32x4*)(b1s + hc * 32 + 16 + g * 4)};
+        f32x8 hf = {};
+#pragma unroll
+        for (int b = 0; b < NBAT; ++b) {
+            if (b + 1 < NBAT) load_batch(hc, b + 1, fb[(b + 1) & 1]);
+            else load_batch(hn, 0, fb[0]);                       // NBAT is even
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const int f = b * NB + i;
+                if (f < 2 * KC) acc1[f & 1] = Mma<float>::k32(fb[b & 1][i], xf[f >> 1], acc1[f & 1]);
+                else acc2[f - 2 * KC] = Mma<float>::k32(fb[b & 1][i], hf, acc2[f - 2 * KC]);
+            }
+            if (b == NBAT / 2 - 1) {                             // fc1 done: GELU on the accumulator layout -> B operand of fc2
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { hf[e] = gelu_for<float>(acc1[0][e]); hf[4 + e] = gelu_for<float>(acc1[1][e]); }
+            }
+        }
+    }
+
+    // ---- reduction over the 8 waves + epilogue, 6 channel tiles per round; wave w < 6 finishes channel tile 6 r + w
+    float* __restrict__ O2 = (float*)p.out2;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+        for (int n = 0; n < 6; ++n) *(f32x4*)(part + (wave * 6 + n) * 256 + lane * 4) = acc2[6 * r + n];
+        __syncthreads();
+        if (wave < 6) {
+            const int c0 = (6 * r + wave) * 16 + g * 4;
+            const f32x4 b2 = *(const f32x4*)(b2s + c0), g2 = *(const f32x4*)(b2s + C + c0);
+            f32x4 sum = *(const f32x4*)(part + (0 * 6 + wave) * 256 + lane * 4);
+#pragma unroll
+            for (int w = 1; w < NW; ++w) sum += *(const f32x4*)(part + (w * 6 + wave) * 256 + lane * 4);
+            float* xs = x1s + l15 * X1_LD + c0;
+            const f32x4 o = *(const f32x4*)xs + g2 * (sum + b2);
+            *(f32x4*)xs = o;
+            if (mok) {
+                *(f32x4*)(X + mrow * p.ldx + c0) = o;
+                if (O2) *(f32x4*)(O2 + mrow * p.ld2 + c0) = o;
+            }
+        }
+        __syncthreads();
+    }
+
+    if (!(p.stats_out || QKV)) return;
+    // ---- statistics of the new rows (every wave, from LDS) and the chained LayerNorm + QKV of the next block
+    f32x8 xq[KC];
+    {
+        float sm = 0.f;
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const f32x4 v = *(const f32x4*)(x1s + l15 * X1_LD + kc * 32 + h * 16 + g * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { xq[kc][h * 4 + e] = v[e]; sm += v[e]; }
+            }
+        sm += __shfl_xor(sm, 16); sm += __shfl_xor(sm, 32);
+        const float mean = sm * (1.f / C);
+        float v = 0.f;
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float dl = xq[kc][e] - mean; v += dl * dl; }
+        v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+        const float rstd = 1.f / sqrtf(v * (1.f / C) + p.eps_next);
+        if (p.stats_out && wave == 0 && mok && g == 0) { p.stats_out[2 * mrow] = mean; p.stats_out[2 * mrow + 1] = rstd; }
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xq[kc][e] = (xq[kc][e] - mean) * rstd;
+    }
+    if (!QKV) return;
+    // Q, K: D[feature][token] -> (B, heads, Tp, hd); V: operands swapped, D[token][feature] -> V^T (B, heads, hd, Tp)
+    constexpr int NTQ = 3 * C / 16, NIT = (NTQ + NW - 1) / NW;
+    const float* __restrict__ WQ = (const float*)p.wqkv + lfrag;
+    float* __restrict__ Qo = (float*)p.q; float* __restrict__ Ko = (float*)p.k; float* __restrict__ Vo = (float*)p.vt;
+    // feature tiles wave, wave + 8, ...: the weights of the next tile are requested before the current one is multiplied
+    f32x8 wq[2][KC];
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) wq[0][kc] = small_load8(WQ + (long)(wave * KC + kc) * 512);
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int nt = wave + it * NW;
+        if (it + 1 < NIT) {
+            const int ntn = nt + NW < NTQ ? nt + NW : NTQ - 1;
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) wq[(it + 1) & 1][kc] = small_load8(WQ + (long)(ntn * KC + kc) * 512);
+        }
+        if (nt >= NTQ) break;                                          // wave-uniform
+        const int sg = nt / (C / 16), nl0 = (nt - sg * (C / 16)) * 16;
+        if (sg < 2) {
+            const int nl = nl0 + g * 4, hh = nl / p.hd, dd = nl - hh * p.hd;
+            f32x4 acc = *(const f32x4*)(bqs + sg * C + nl);
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) acc = Mma<float>::k32(wq[it & 1][kc], xq[kc], acc);
+            const int mq = (int)m0 + l15, bq_ = mq / p.Tp;
+            if (mq < p.M) {
+                float* dst = (sg == 0 ? Qo : Ko) + ((long)bq_ * p.heads * p.Tp + (mq - bq_ * p.Tp)) * p.hd + (long)hh * p.Tp * p.hd + dd;
+                *(f32x4*)dst = acc * (sg == 0 ? p.qscale : 1.f);
+            }
+        } else {
+            const int nl = nl0 + l15, hh = nl / p.hd, dd = nl - hh * p.hd;
+            const float bb = bqs[2 * C + nl];
+            f32x4 acc = {bb, bb, bb, bb};
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) acc = Mma<float>::k32(xq[kc], wq[it & 1][kc], acc);
+            const int mv = (int)m0 + g * 4, bv_ = mv / p.Tp;
+            if (mv < p.M)
+                *(f32x4*)(Vo + (long)bv_ * p.heads * p.hd * p.Tp + (mv - bv_ * p.Tp) + ((long)hh * p.hd + dd) * p.Tp) = acc;   // M, Tp multiples of 4: whole 4-token run
+        }
+    }
+}
+template <> __global__ __launch_bounds__(NTHR, 1) void mlp_small_kernel<float, true, 1, true>(const MlpParams p) { mlp_small_f32<true>(p); }
+template <> __global__ __launch_bounds__(NTHR, 1) void mlp_small_kernel<float, false, 1, true>(const MlpParams p) { mlp_small_f32<false>(p); }
+
 constexpr long MLP_SMALL_TT1_MAX_ROWS = 3200;      // one or two 640 x 640 images: 16-token workgroups (see mlp_small_kernel)
 template <typename T, bool QKV, int TT, bool FRAG = false>
 int launch_mlp_small_tt(const MlpParams& p, hipStream_t st) {
@@ -953,8 +1185,14 @@ extern "C" int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, cons
                                     int heads, int hd, int Tp, int dtype, void* hip_stream) {
     if (!x || !w1_frag || !b1_folded || !w2_chunked || !b2 || !gamma2 || !att || !wp_frag || !bp || !gamma1 || M < 0) return LWDETR_ERR_BAD_ARG;
     if (M == 0) return LWDETR_OK;
-    if (C != 192 || (dtype != DT_F16 && dtype != DT_BF16) || M >= MLP_SMALL_MAX_ROWS) return LWDETR_ERR_UNSUPPORTED;
-    if (ldx % 8 != 0 || (out2 && ld2 % 8 != 0) || ldatt % 8 != 0) return LWDETR_ERR_BAD_ARG;
+    if (C != 192 || (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_BF16) || M >= MLP_SMALL_MAX_ROWS) return LWDETR_ERR_UNSUPPORTED;
+    if (dtype == DT_F32) {
+        // f32: rows, fragments and runs of 4 values move in 16-byte pieces (two per 8 values); the bias / LayerScale vectors likewise. Refused before any launch
+        auto mis = [](const void* q) { return ((size_t)q & 15) != 0; };
+        if (ldx % 4 != 0 || (out2 && ld2 % 4 != 0) || ldatt % 4 != 0 || mis(x) || mis(att) || mis(out2) || mis(w1_frag) || mis(wp_frag) || mis(wqkv_frag_next) ||
+            mis(w2_chunked) || mis(b1_folded) || mis(b2) || mis(bp) || mis(gamma1) || mis(gamma2) || mis(bqkv_next) || mis(q_out) || mis(k_out) || mis(vt_out))
+            return LWDETR_ERR_UNSUPPORTED;
+    } else if (ldx % 8 != 0 || (out2 && ld2 % 8 != 0) || ldatt % 8 != 0) return LWDETR_ERR_BAD_ARG;
     if (wqkv_frag_next && (!bqkv_next || !q_out || !k_out || !vt_out || heads <= 0 || hd % 4 != 0 || heads * hd != C || Tp % 4 != 0 || M % 4 != 0))
         return LWDETR_ERR_BAD_ARG;
     MlpParams p;
@@ -966,6 +1204,8 @@ extern "C" int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, cons
     p.out2 = out2; p.ld2 = ld2; p.stats_out = stats_out; p.M = M; p.eps = eps; p.eps_next = eps_next;
     p.partial = nullptr; p.chunks_per_split = 0; p.ntiles = 0;
     hipStream_t st = (hipStream_t)hip_stream;
+    // f32: 16-token workgroups at every row count - TT = 2 is not built (registers: see mlp_small_f32), so LWDETR_MLP_SMALL_TT is ignored here
+    if (dtype == DT_F32) return p.wqkv ? launch_mlp_small_tt<float, true, 1, true>(p, st) : launch_mlp_small_tt<float, false, 1, true>(p, st);
     if (dtype == DT_F16) return p.wqkv ? launch_mlp_small<f16, true>(p, st) : launch_mlp_small<f16, false>(p, st);
     return p.wqkv ? launch_mlp_small<bf16, true>(p, st) : launch_mlp_small<bf16, false>(p, st);
 }

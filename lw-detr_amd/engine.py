@@ -314,7 +314,8 @@ class ForwardPlan:
                 cls = K.MlpFusedOp
                 if K.vit_block_few_supported(C, self.T, rows):
                     # round 6: the few-token kernel loads its weights straight from L2 as MFMA fragments - hand them over fragment-major (one
-                    # contiguous KB per fragment instead of 16 half lines): 30 -> 22 us per block launch at one image
+                    # contiguous KB per fragment instead of 16 half lines): 30 -> 22 us per block launch at one image. float32 comes here only with
+                    # LWDETR_VIT_BLOCK_FEW_F32=1 (then `fused` above is true below MLP_FUSED_MIN_ROWS too: no hid buffer, block 0 keeps LayerNorm + QKV GEMM)
                     cls = K.VitBlockFewOp
                     w1f = pw.custom(blk + ".mlp.fc1.frag", lambda w1f=w1f: K.pack_frag16(w1f))
                     wp_ = pw.custom(blk + ".attn.proj.frag", lambda wp_=wp_: K.pack_frag16(wp_))

@@ -338,7 +338,8 @@ def mlp_fused_supported(C_, dtype, rows=None) -> bool:
         return force == "1"
     if C_ == 192 and dtype in (torch.float16, torch.bfloat16):
         return True             # lwdetr_mlp_fused switches to its tile-per-workgroup kernel below MLP_FUSED_MIN_ROWS by itself
-    return rows >= MLP_FUSED_MIN_ROWS
+    # float32 below MLP_FUSED_MIN_ROWS: only where the plan takes the few-token block kernel (LWDETR_VIT_BLOCK_FEW_F32=1; off by default)
+    return rows >= MLP_FUSED_MIN_ROWS or vit_block_few_supported(C_, dtype, rows)
 
 
 _KSLOT_PERM = [4 * g_ + e + 16 * hi for g_ in range(4) for hi in range(2) for e in range(4)]
@@ -404,13 +405,39 @@ class MlpFusedOp:
 
 
 VIT_BLOCK_FEW_MAX_ROWS = 12800      # = MLP_SMALL_MAX_ROWS of csrc/mlp.hip
+VIT_BLOCK_FEW_F32_MAX_ROWS = 3201   # float32: up to two 640 x 640 images the launch measured faster than the launches it replaces; slower at 4800 rows (profiles/r7b_*, (3))
 
 
 def vit_block_few_supported(C_, dtype, rows) -> bool:
     """The launch-plan choice for lwdetr_vit_block_few (the few-token block kernel on fragment-major weights): 16-bit C = 192 below
-    ~8 images of 640 x 640. LWDETR_VIT_BLOCK_FEW=0 keeps the row-major form (lwdetr_mlp_fused; A/B runs)."""
-    return (C_ == 192 and dtype in (torch.float16, torch.bfloat16) and rows is not None and rows < VIT_BLOCK_FEW_MAX_ROWS
-            and os.environ.get("LWDETR_VIT_BLOCK_FEW", "1") != "0")
+    ~8 images of 640 x 640. LWDETR_VIT_BLOCK_FEW=0 keeps the row-major form (lwdetr_mlp_fused; A/B runs). float32 only with
+    LWDETR_VIT_BLOCK_FEW_F32=1 (read when a plan is built; off by default) and below VIT_BLOCK_FEW_F32_MAX_ROWS: without the switch an fp32
+    plan runs LayerNorm, QKV, attention, projection, LayerNorm, fc1, fc2 as seven launches per block (measured in profiles/r7b_vit_block_few_f32.txt)."""
+    if C_ != 192 or rows is None or os.environ.get("LWDETR_VIT_BLOCK_FEW", "1") == "0":
+        return False
+    if dtype == torch.float32:
+        return os.environ.get("LWDETR_VIT_BLOCK_FEW_F32", "0") == "1" and rows < VIT_BLOCK_FEW_F32_MAX_ROWS
+    return dtype in (torch.float16, torch.bfloat16) and rows < VIT_BLOCK_FEW_MAX_ROWS
+
+
+def vit_block_few_entry_takes(dtype, M, C_, *, x, ldx, att, ldatt, w1, b1, w2, b2, gamma2, wp, bp, gamma1, out2=None, ld2=0, wqkv=None, bqkv=None,
+                              q=None, k=None, vt=None, heads=0, hd=0, Tp=0) -> bool:
+    """The host-side conditions of lwdetr_vit_block_few (mlp.hip) on addresses (integers; None / 0 = absent) and strides in elements of ``dtype``:
+    C = 192, 0 <= M < VIT_BLOCK_FEW_MAX_ROWS, every mandatory operand present; with the chained QKV its bias and the three destinations, heads * hd = C,
+    hd % 4, Tp % 4, M % 4. 16-bit: ldx / ld2 / ldatt % 8. float32: ldx / ld2 / ldatt % 4 and x, att, out2, q, k, vt, the three fragment-major weights,
+    the chunk-major fc2 weight and the six f32 vectors 16-byte aligned (rows, fragments and runs of 4 values move in 16-byte pieces)."""
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16) or C_ != 192 or not 0 <= M < VIT_BLOCK_FEW_MAX_ROWS:
+        return False
+    if not all((x, att, w1, b1, w2, b2, gamma2, wp, bp, gamma1)):
+        return False
+    if wqkv and (not all((bqkv, q, k, vt)) or heads <= 0 or hd % 4 != 0 or heads * hd != C_ or Tp % 4 != 0 or M % 4 != 0):
+        return False
+    run = 4 if dtype == torch.float32 else 8
+    if ldx % run != 0 or ldatt % run != 0 or (out2 and ld2 % run != 0):
+        return False
+    if dtype == torch.float32:
+        return all((a or 0) % 16 == 0 for a in (x, att, out2, w1, wp, wqkv, w2, b1, b2, bp, gamma1, gamma2, bqkv, q, k, vt))
+    return True
 
 
 class VitBlockFewOp(MlpFusedOp):
@@ -419,6 +446,11 @@ class VitBlockFewOp(MlpFusedOp):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         assert k.get("att") is not None
+        (x, ldx, w1, b1, w2, b2, gamma2, out2, ld2, _stats, M, C_, _eps, _eps_next, att, ldatt, wp, bp, gamma1, wqkv, bqkv, q, k_, vt, _qscale,
+         heads, hd, Tp, _code) = self.args
+        assert vit_block_few_entry_takes(a[0].dtype, M, C_, x=x, ldx=ldx, att=att, ldatt=ldatt, w1=w1, b1=b1, w2=w2, b2=b2, gamma2=gamma2, wp=wp, bp=bp,
+                                         gamma1=gamma1, out2=out2, ld2=ld2, wqkv=wqkv, bqkv=bqkv, q=q, k=k_, vt=vt, heads=heads, hd=hd, Tp=Tp), \
+            "lwdetr_vit_block_few does not take these operands (see vit_block_few_entry_takes)"
         self._fn = _nat.lib().lwdetr_vit_block_few
 
 
