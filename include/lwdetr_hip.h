@@ -250,12 +250,17 @@ int lwdetr_mlp_fused(void* x, long ldx, const void* w1_folded, const float* b1_f
                      const float* gamma1, const void* wqkv_next, const float* bqkv_next, void* q_out, void* k_out,
                      void* vt_out, float qscale, int heads, int hd, int Tp, int dtype, void* hip_stream);
 
-/* The few-token form of lwdetr_mlp_fused with the attention projection (round 6; C = 192, M < 12800: the single-image latency path) on
+/* The few-token form of lwdetr_mlp_fused with the attention projection (round 6; C in {192, 384}, M < 12800: the single-image latency path) on
  * FRAGMENT-MAJOR weights: w1_frag, wp_frag, wqkv_frag_next = the w1_folded / wp / wqkv_next of lwdetr_mlp_fused re-laid out as
  * [R / 16][C / 32][16][32] (lwdetr_amd.kernels.pack_frag16), so that each 16 x 32 MFMA fragment the kernel loads straight from L2 is one
- * contiguous KB (2 KB in float32) instead of 16 half lines. Everything else as lwdetr_mlp_fused (att required); in 16-bit the results are
- * bit-identical to it.
+ * contiguous KB (2 KB in float32) instead of 16 half lines. Everything else as lwdetr_mlp_fused (att required); in 16-bit at C = 192 the
+ * results are bit-identical to it.
+ * Accepted: C = 192 with dtype 0 / 1 / 2, C = 384 with dtype 1 / 2 only (C = 384 with dtype 0: LWDETR_ERR_UNSUPPORTED).
  * dtype 1 / 2 (f16 / bf16): ldx, ld2, ldatt multiples of 8 (LWDETR_ERR_BAD_ARG otherwise).
+ * 16-bit C = 384 (vit_block_few384_kernel, a kernel of its own: 16-token workgroups at every M, hidden activations through LDS, each wave owns
+ * output channel tiles over the whole hidden dimension; LWDETR_MLP_SMALL_TT / LWDETR_MLP_SMALL do not apply): the same argument rules as 16-bit
+ * C = 192 - its widest access is 8 values at a multiple of 8 elements of a row, as there. Roundings as lwdetr_mlp_fused at C = 384, but NOT
+ * bit-identical to it: equal to rounding only.
  * dtype 0 (float32; the same structure on exact-f32 16x16x4 MFMAs, 16-token workgroups at every M; sums in another order than lwdetr_mlp_fused's
  * f32 kernel, so equal to it only to rounding): ldx, ld2, ldatt multiples of 4, and x, att, out2, q_out, k_out, vt_out, w1_frag, wp_frag,
  * wqkv_frag_next, w2_chunked, b1_folded, b2, bp, gamma1, gamma2, bqkv_next 16-byte aligned - LWDETR_ERR_UNSUPPORTED otherwise, before any launch.

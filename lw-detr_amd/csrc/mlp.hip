@@ -21,6 +21,7 @@
 //              (mean, rstd) of the NEW x for the next block's LayerNorm, which the QKV GEMM applies on load.
 // LDS row strides are == 2 (mod 4) sixteen-byte slots: conflict-free for the 16-lane ds_read_b128 service groups.
 #include "common.h"
+#include "vit_block_few384.h"
 #include <cstdlib>
 
 #ifndef MLP_WAVES_PER_SIMD
@@ -1185,7 +1186,8 @@ extern "C" int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, cons
                                     int heads, int hd, int Tp, int dtype, void* hip_stream) {
     if (!x || !w1_frag || !b1_folded || !w2_chunked || !b2 || !gamma2 || !att || !wp_frag || !bp || !gamma1 || M < 0) return LWDETR_ERR_BAD_ARG;
     if (M == 0) return LWDETR_OK;
-    if (C != 192 || (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_BF16) || M >= MLP_SMALL_MAX_ROWS) return LWDETR_ERR_UNSUPPORTED;
+    if ((C != 192 && C != 384) || (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_BF16) || M >= MLP_SMALL_MAX_ROWS) return LWDETR_ERR_UNSUPPORTED;
+    if (C == 384 && dtype == DT_F32) return LWDETR_ERR_UNSUPPORTED;           // the C = 384 form is 16-bit only
     if (dtype == DT_F32) {
         // f32: rows, fragments and runs of 4 values move in 16-byte pieces (two per 8 values); the bias / LayerScale vectors likewise. Refused before any launch
         auto mis = [](const void* q) { return ((size_t)q & 15) != 0; };
@@ -1204,6 +1206,17 @@ extern "C" int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, cons
     p.out2 = out2; p.ld2 = ld2; p.stats_out = stats_out; p.M = M; p.eps = eps; p.eps_next = eps_next;
     p.partial = nullptr; p.chunks_per_split = 0; p.ntiles = 0;
     hipStream_t st = (hipStream_t)hip_stream;
+    if (C == 384) {
+        // 16-bit C = 384: vit_block_few384_kernel (vit_block_few384.hip), 16-token workgroups at every row count; LWDETR_MLP_SMALL_TT and LWDETR_MLP_SMALL do
+        // not apply. Its widest accesses are those of the 16-bit C = 192 kernel (8 values at multiples of 8 elements of a row): the stride rules above cover them
+        VitFew384Params f;
+        f.x = x; f.ldx = ldx; f.att = att; f.ldatt = ldatt; f.wp = wp_frag; f.bp = bp; f.gamma1 = gamma1;
+        f.w1 = w1_frag; f.b1 = b1_folded; f.w2p = w2_chunked; f.b2 = b2; f.gamma2 = gamma2;
+        f.out2 = out2; f.ld2 = ld2; f.stats_out = stats_out;
+        f.wqkv = wqkv_frag_next; f.bqkv = bqkv_next; f.q = q_out; f.k = k_out; f.vt = vt_out; f.qscale = qscale; f.heads = heads; f.hd = hd; f.Tp = Tp;
+        f.M = M; f.eps = eps; f.eps_next = eps_next;
+        return lwdetr_vit_block_few384_launch(f, dtype, st);
+    }
     // f32: 16-token workgroups at every row count - TT = 2 is not built (registers: see mlp_small_f32), so LWDETR_MLP_SMALL_TT is ignored here
     if (dtype == DT_F32) return p.wqkv ? launch_mlp_small_tt<float, true, 1, true>(p, st) : launch_mlp_small_tt<float, false, 1, true>(p, st);
     if (dtype == DT_F16) return p.wqkv ? launch_mlp_small<f16, true>(p, st) : launch_mlp_small<f16, false>(p, st);

@@ -315,7 +315,8 @@ class ForwardPlan:
                 if K.vit_block_few_supported(C, self.T, rows):
                     # round 6: the few-token kernel loads its weights straight from L2 as MFMA fragments - hand them over fragment-major (one
                     # contiguous KB per fragment instead of 16 half lines): 30 -> 22 us per block launch at one image. float32 comes here only with
-                    # LWDETR_VIT_BLOCK_FEW_F32=1 (then `fused` above is true below MLP_FUSED_MIN_ROWS too: no hid buffer, block 0 keeps LayerNorm + QKV GEMM)
+                    # LWDETR_VIT_BLOCK_FEW_F32=1 (then `fused` above is true below MLP_FUSED_MIN_ROWS too: no hid buffer, block 0 keeps LayerNorm + QKV GEMM),
+                    # 16-bit C = 384 only with LWDETR_VIT_BLOCK_FEW_C384=1 (the same: vit_block_few384_kernel, one launch per block)
                     cls = K.VitBlockFewOp
                     w1f = pw.custom(blk + ".mlp.fc1.frag", lambda w1f=w1f: K.pack_frag16(w1f))
                     wp_ = pw.custom(blk + ".attn.proj.frag", lambda wp_=wp_: K.pack_frag16(wp_))

@@ -338,7 +338,8 @@ def mlp_fused_supported(C_, dtype, rows=None) -> bool:
         return force == "1"
     if C_ == 192 and dtype in (torch.float16, torch.bfloat16):
         return True             # lwdetr_mlp_fused switches to its tile-per-workgroup kernel below MLP_FUSED_MIN_ROWS by itself
-    # float32 below MLP_FUSED_MIN_ROWS: only where the plan takes the few-token block kernel (LWDETR_VIT_BLOCK_FEW_F32=1; off by default)
+    # float32, and 16-bit C = 384, below MLP_FUSED_MIN_ROWS: only where the plan takes the few-token block kernel (LWDETR_VIT_BLOCK_FEW_F32=1 /
+    # LWDETR_VIT_BLOCK_FEW_C384=1; both off by default)
     return rows >= MLP_FUSED_MIN_ROWS or vit_block_few_supported(C_, dtype, rows)
 
 
@@ -406,15 +407,21 @@ class MlpFusedOp:
 
 VIT_BLOCK_FEW_MAX_ROWS = 12800      # = MLP_SMALL_MAX_ROWS of csrc/mlp.hip
 VIT_BLOCK_FEW_F32_MAX_ROWS = 3201   # float32: up to two 640 x 640 images the launch measured faster than the launches it replaces; slower at 4800 rows (profiles/r7b_*, (3))
+VIT_BLOCK_FEW_C384_MAX_ROWS = 3201  # 16-bit C = 384: per launch faster than the six launches it replaces at 1600 and 3200 rows, slower at 4800 (profiles/r7c_*, (3)); the single-image HIP graph measured slower with it, (4)
 
 
 def vit_block_few_supported(C_, dtype, rows) -> bool:
     """The launch-plan choice for lwdetr_vit_block_few (the few-token block kernel on fragment-major weights): 16-bit C = 192 below
     ~8 images of 640 x 640. LWDETR_VIT_BLOCK_FEW=0 keeps the row-major form (lwdetr_mlp_fused; A/B runs). float32 only with
     LWDETR_VIT_BLOCK_FEW_F32=1 (read when a plan is built; off by default) and below VIT_BLOCK_FEW_F32_MAX_ROWS: without the switch an fp32
-    plan runs LayerNorm, QKV, attention, projection, LayerNorm, fc1, fc2 as seven launches per block (measured in profiles/r7b_vit_block_few_f32.txt)."""
-    if C_ != 192 or rows is None or os.environ.get("LWDETR_VIT_BLOCK_FEW", "1") == "0":
+    plan runs LayerNorm, QKV, attention, projection, LayerNorm, fc1, fc2 as seven launches per block (measured in profiles/r7b_vit_block_few_f32.txt).
+    16-bit C = 384 (medium, large) only with LWDETR_VIT_BLOCK_FEW_C384=1 (read when a plan is built; off by default) and below
+    VIT_BLOCK_FEW_C384_MAX_ROWS; without it those plans keep their seven launches per block (profiles/r7c_vit_block_few_c384.txt). Never float32 at C = 384."""
+    if C_ not in (192, 384) or rows is None or os.environ.get("LWDETR_VIT_BLOCK_FEW", "1") == "0":
         return False
+    if C_ == 384:       # vit_block_few384_kernel: 16-bit only, behind its own switch
+        return (dtype in (torch.float16, torch.bfloat16) and os.environ.get("LWDETR_VIT_BLOCK_FEW_C384", "0") == "1"
+                and rows < VIT_BLOCK_FEW_C384_MAX_ROWS)
     if dtype == torch.float32:
         return os.environ.get("LWDETR_VIT_BLOCK_FEW_F32", "0") == "1" and rows < VIT_BLOCK_FEW_F32_MAX_ROWS
     return dtype in (torch.float16, torch.bfloat16) and rows < VIT_BLOCK_FEW_MAX_ROWS
@@ -423,10 +430,12 @@ def vit_block_few_supported(C_, dtype, rows) -> bool:
 def vit_block_few_entry_takes(dtype, M, C_, *, x, ldx, att, ldatt, w1, b1, w2, b2, gamma2, wp, bp, gamma1, out2=None, ld2=0, wqkv=None, bqkv=None,
                               q=None, k=None, vt=None, heads=0, hd=0, Tp=0) -> bool:
     """The host-side conditions of lwdetr_vit_block_few (mlp.hip) on addresses (integers; None / 0 = absent) and strides in elements of ``dtype``:
-    C = 192, 0 <= M < VIT_BLOCK_FEW_MAX_ROWS, every mandatory operand present; with the chained QKV its bias and the three destinations, heads * hd = C,
+    C = 192 (any of the three dtypes) or C = 384 (16-bit only), 0 <= M < VIT_BLOCK_FEW_MAX_ROWS, every mandatory operand present; with the chained QKV its bias and the three destinations, heads * hd = C,
     hd % 4, Tp % 4, M % 4. 16-bit: ldx / ld2 / ldatt % 8. float32: ldx / ld2 / ldatt % 4 and x, att, out2, q, k, vt, the three fragment-major weights,
     the chunk-major fc2 weight and the six f32 vectors 16-byte aligned (rows, fragments and runs of 4 values move in 16-byte pieces)."""
-    if dtype not in (torch.float32, torch.float16, torch.bfloat16) or C_ != 192 or not 0 <= M < VIT_BLOCK_FEW_MAX_ROWS:
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16) or C_ not in (192, 384) or not 0 <= M < VIT_BLOCK_FEW_MAX_ROWS:
+        return False
+    if C_ == 384 and dtype == torch.float32:
         return False
     if not all((x, att, w1, b1, w2, b2, gamma2, wp, bp, gamma1)):
         return False

@@ -1,8 +1,8 @@
 """Per-launch time of lwdetr_vit_block_few (projection + MLP + the next block's norm1 / QKV, one launch) on synthetic operands: HIP events, the median
 of 30 single launches (each followed by a synchronise) and the mean of 200 launches issued back to back.
 
-    python tools/vit_block_few_time.py [--dtype fp32|fp16|bf16] [--rows 1600:1600,3200:1600,6400:1600,12000:400]
-rows are M:Tp pairs. LWDETR_HIP_LIB selects a tuning build of the library (e.g. one compiled with TUNE=-DMLP_SMALL_F32_NB=6). The seven launches an fp32
+    python tools/vit_block_few_time.py [--dtype fp32|fp16|bf16] [--c 192|384] [--rows 1600:1600,3200:1600,6400:1600,12000:400]
+rows are M:Tp pairs; --c 384 (12 heads of 32, 16-bit only) times vit_block_few384_kernel. LWDETR_HIP_LIB selects a tuning build of the library (e.g. one compiled with TUNE=-DMLP_SMALL_F32_NB=6). The seven launches an fp32
 plan runs per block without LWDETR_VIT_BLOCK_FEW_F32 are timed by tools/op_times.py --dtype fp32."""
 import argparse
 import os
@@ -15,13 +15,16 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16", "bf16"])
+    ap.add_argument("--c", type=int, default=192, choices=[192, 384])
     ap.add_argument("--rows", default="1600:1600,3200:1600,6400:1600,12000:400")
     a = ap.parse_args()
     import torch
     from lwdetr_amd import _native, kernels as K
     T = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}[a.dtype]
     dev = torch.device("cuda:0")
-    c, heads, hd = 192, 12, 16
+    c, heads, hd = a.c, 12, a.c // 12
+    if c == 384 and a.dtype == "fp32":
+        sys.exit("lwdetr_vit_block_few has no float32 form at C = 384")
     gen = torch.Generator().manual_seed(0)
     rnd = lambda *s, scale=1.0: (torch.randn(*s, generator=gen) * scale).to(dev)
     w1, b1, w2, b2 = rnd(4 * c, c, scale=c ** -0.5), rnd(4 * c) * 0.1, rnd(c, 4 * c, scale=(4 * c) ** -0.5), rnd(c) * 0.1
@@ -30,7 +33,7 @@ def main():
     w1p, b1p, w2p = K.pack_mlp_weights(w1, b1, w2, lw, lb, T, proj=True)
     wq, bq = K.pack_qkv_weights(wqkv, qb, vb, lw, lb, T)
     w1F, wpF, wqF = K.pack_frag16(w1p), K.pack_frag16(wp.to(T).contiguous()), K.pack_frag16(wq)
-    print(f"library {_native.LIB_PATH}  device {torch.cuda.get_device_name(0)}  dtype {a.dtype}")
+    print(f"library {_native.LIB_PATH}  device {torch.cuda.get_device_name(0)}  dtype {a.dtype}  C {c}")
     for pair in a.rows.split(","):
         m, tp = (int(v) for v in pair.split(":"))
         nb = m // tp
