@@ -297,9 +297,25 @@ int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, const void*
  * destination row b * S + lsi + row % npix of the (total_rows, D) tensors; k5 == 0: `memory` rows themselves (npix = S, lsi = 0).
  * wstream / vec: lwdetr_amd.kernels.pack_enc_chain (4 KB pieces of 32 output channels x 64 k-slots in MFMA lane order, consumption
  * order cv2 | values | enc_output | class, + 2 zero pieces; f32 vectors [b2 | ln_w | ln_b] | b_enc | g_enc | be_enc | b_cls[96] | b_val);
- * sizes from the helpers. D in {256, 384}; k5 in {0, 640 (D = 256)}. */
+ * sizes from the helpers. D in {256, 384}; k5 in {0, 640 (D = 256)}.
+ * Class count: 1 <= ncls <= 96 is the form above (3 class tiles of 32 columns). 96 < ncls <= 384 (Objects365: 366) takes the wide kernels
+ * (12 class tiles): the class weight and bias of the stream / vec are zero-padded to 384 rows (b_cls[384]; pack_enc_chain does it by the
+ * class count), `cls` has a row stride ld_cls >= 384 (ld_cls % 8 == 0 in both forms), columns [ncls, 384) are written as zeros and the row
+ * maximum runs over columns < ncls only. lwdetr_enc_chain_class_cols(ncls) = 96 or 384 is that column count (LWDETR_ERR_BAD_ARG for
+ * ncls < 1 or > 384); the _cls helpers give the sizes for a class count and equal the two older ones up to 96 classes (those keep the
+ * narrow form's values). A class count / ld_cls that do not fit are LWDETR_ERR_BAD_ARG before any launch, as every other argument rule;
+ * the 2 GB range of the row tensors (LWDETR_ERR_UNSUPPORTED) counts the real ld_cls.
+ * lwdetr_enc_chain_check: the argument checks of lwdetr_enc_chain alone - what it would answer before launching (LWDETR_OK: it would
+ * launch, or M == 0); no device call, no pointer is dereferenced. */
 long lwdetr_enc_chain_vec_floats(int D, int k5);
 long lwdetr_enc_chain_pieces(int D, int k5, int nl);
+long lwdetr_enc_chain_class_cols(int ncls);
+long lwdetr_enc_chain_vec_floats_cls(int D, int k5, int ncls);
+long lwdetr_enc_chain_pieces_cls(int D, int k5, int nl, int ncls);
+int lwdetr_enc_chain_check(const void* in, long ld_in, int k5, void* memory, void* om, void* cls, long ld_cls, float* cls_max,
+                           void* const* values, int nl, const unsigned char* rowvalid, const unsigned char* notpad,
+                           const void* wstream, const float* vec, long M, int D, int npix, int S, int lsi, long total_rows,
+                           int ncls, int dtype);
 int lwdetr_enc_chain(const void* in, long ld_in, int k5, void* memory, void* om, void* cls, long ld_cls, float* cls_max,
                      void* const* values, int nl, const unsigned char* rowvalid, const unsigned char* notpad,
                      const void* wstream, const float* vec, long M, int D, int npix, int S, int lsi, long total_rows,

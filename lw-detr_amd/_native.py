@@ -132,6 +132,13 @@ def lib():
         l.lwdetr_enc_chain_vec_floats.restype = C.c_long
         l.lwdetr_enc_chain_pieces.argtypes = [i, i, i]
         l.lwdetr_enc_chain_pieces.restype = C.c_long
+        l.lwdetr_enc_chain_class_cols.argtypes = [i]
+        l.lwdetr_enc_chain_class_cols.restype = C.c_long
+        l.lwdetr_enc_chain_vec_floats_cls.argtypes = [i, i, i]
+        l.lwdetr_enc_chain_vec_floats_cls.restype = C.c_long
+        l.lwdetr_enc_chain_pieces_cls.argtypes = [i, i, i, i]
+        l.lwdetr_enc_chain_pieces_cls.restype = C.c_long
+        l.lwdetr_enc_chain_check.argtypes = [vp, lg, i, vp, vp, vp, lg, vp, vp, i, vp, vp, vp, vp, lg, i, i, i, i, lg, i, i]
         l.lwdetr_row_chain.argtypes = [C.POINTER(ChainDesc), i, vp]
         l.lwdetr_row_chain_pieces.argtypes = [C.POINTER(ChainDesc)]
         l.lwdetr_row_chain_pieces.restype = C.c_long
@@ -153,7 +160,7 @@ def lib():
         l.lwdetr_prof_kernel_name.restype = C.c_char_p
         l.lwdetr_prof_collect.argtypes = [vp, vp, vp, vp, i]
         for fn in ("lwdetr_msda_forward", "lwdetr_msda_backward", "lwdetr_msda_fused_forward", "lwdetr_gemm", "lwdetr_attention",
-                   "lwdetr_layernorm", "lwdetr_layernorm_chain", "lwdetr_row_stats", "lwdetr_enc_chain", "lwdetr_row_chain", "lwdetr_mlp_fused", "lwdetr_vit_block_few", "lwdetr_vit_block", "lwdetr_vit_qkv", "lwdetr_vit_stem", "lwdetr_ffn_splits", "lwdetr_ffn_partial", "lwdetr_ffn_finish", "lwdetr_select_gather", "lwdetr_decoder_inputs",
+                   "lwdetr_layernorm", "lwdetr_layernorm_chain", "lwdetr_row_stats", "lwdetr_enc_chain", "lwdetr_enc_chain_check", "lwdetr_row_chain", "lwdetr_mlp_fused", "lwdetr_vit_block_few", "lwdetr_vit_block", "lwdetr_vit_qkv", "lwdetr_vit_stem", "lwdetr_ffn_splits", "lwdetr_ffn_partial", "lwdetr_ffn_finish", "lwdetr_select_gather", "lwdetr_decoder_inputs",
                    "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
             getattr(l, fn).restype = C.c_int
         _lib = l

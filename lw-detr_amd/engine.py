@@ -360,7 +360,8 @@ class ForwardPlan:
         self.memory = z(B * self.S, d)
         self.level_feats = []
         # round 4: everything between the C2f block and the two-stage top-k as ONE launch (lwdetr_enc_chain, built in
-        # _build_transformer); with one level and d = 256 the chain also takes the projector's cv2 + LayerNorm in front
+        # _build_transformer); with one level and d = 256 the chain also takes the projector's cv2 + LayerNorm in front.
+        # More than 96 classes (up to 384): only with LWDETR_CHAIN_WIDE_CLS=1 (kernels.enc_chain_supported)
         self.use_chain = K.enc_chain_supported(d, self.T, ncls=pw.sd["class_embed.weight"].shape[0], nl=cfg.dec_layers, rows=B * self.S)
         self.chain_front = None
         for li, name in enumerate(cfg.projector_scale):
@@ -453,7 +454,7 @@ class ForwardPlan:
         self.ncls = pw.sd["class_embed.weight"].shape[0]
         self.ldc = _ceil4(self.ncls)
         nl = cfg.dec_layers
-        self.ldc_enc = 96 if self.use_chain else self.ldc
+        self.ldc_enc = K.enc_chain_class_cols(self.ncls) if self.use_chain else self.ldc
         self.enc_cls = z(B * S, self.ldc_enc)
         self.cls_max = self._own(torch.zeros(B, S, dtype=torch.float32, device=dev))
         ops = self.ops_enc

@@ -660,9 +660,22 @@ class VitBlockOp:
 CHAIN_MIN_ROWS = 2048           # below this the separate launches spread over more CUs than M / 128 workgroups would
 
 
+ENC_CHAIN_NARROW_COLS, ENC_CHAIN_WIDE_COLS = 96, 384     # class columns of the two forms of lwdetr_enc_chain (lwdetr_enc_chain_class_cols)
+
+
+def enc_chain_class_cols(ncls) -> int:
+    """Class columns (weight rows, bias entries, minimum ld_cls) lwdetr_enc_chain works on for ``ncls`` classes: 96 up to 96 classes, 384 up to 384
+    (the wide kernels); restates lwdetr_enc_chain_class_cols so that packing needs no library."""
+    if not 1 <= ncls <= ENC_CHAIN_WIDE_COLS:
+        raise ValueError(f"lwdetr_enc_chain takes 1 .. {ENC_CHAIN_WIDE_COLS} classes, not {ncls}")
+    return ENC_CHAIN_NARROW_COLS if ncls <= ENC_CHAIN_NARROW_COLS else ENC_CHAIN_WIDE_COLS
+
+
 def enc_chain_supported(d, dtype, k5=0, ncls=91, nl=3, rows=None) -> bool:
-    """Shapes / dtypes lwdetr_enc_chain is instantiated for; with ``rows`` the launch-plan choice (LWDETR_CHAIN=0/1 forces)."""
-    ok = dtype in (torch.float16, torch.bfloat16) and ((d == 256 and k5 in (0, 640)) or (d == 384 and k5 == 0)) and ncls <= 96 and 1 <= nl <= 6
+    """Shapes / dtypes lwdetr_enc_chain is instantiated for; with ``rows`` the launch-plan choice (LWDETR_CHAIN=0/1 forces).
+    More than 96 classes (up to 384: the wide kernels) only with LWDETR_CHAIN_WIDE_CLS=1, read when a plan is built."""
+    ok = dtype in (torch.float16, torch.bfloat16) and ((d == 256 and k5 in (0, 640)) or (d == 384 and k5 == 0)) and 1 <= nl <= 6
+    ok = ok and (ncls <= ENC_CHAIN_NARROW_COLS or (ncls <= ENC_CHAIN_WIDE_COLS and os.environ.get("LWDETR_CHAIN_WIDE_CLS") == "1"))
     if not ok or rows is None:
         return ok
     force = os.environ.get("LWDETR_CHAIN")
@@ -699,14 +712,15 @@ def chain_pieces_split(w, kslots=None):
 def pack_enc_chain(d, dtype, w_enc, b_enc, g_enc, be_enc, w_cls, b_cls, w_val, b_val, cv2=None):
     """Host-side packing for lwdetr_enc_chain (f32 master tensors in) -> (stream of ``dtype``, vec f32).
     cv2 = (w2 (d, k5) BatchNorm-folded, b2 (d), ln_w (d), ln_b (d)) or None. Consumption order: cv2 | values | enc_output | class | 2 zero
-    pieces. Operands that come from memory (cv2's input; without cv2 the `memory` rows) are in natural k order, operands handed on
+    pieces. The class weight and bias are zero-padded to enc_chain_class_cols(ncls) rows: 96, or 384 for more than 96 classes. Operands that come from memory (cv2's input; without cv2 the `memory` rows) are in natural k order, operands handed on
     from an accumulator (after a LayerNorm) in k-slot order."""
     f = lambda t: t.detach().float().cpu()
     w_enc, b_enc, g_enc, be_enc, w_cls, b_cls, w_val, b_val = map(f, (w_enc, b_enc, g_enc, be_enc, w_cls, b_cls, w_val, b_val))
     perm = vb_kslot_channels(d)
     mem_slots = perm if cv2 is not None else None
     ncls = w_cls.shape[0]
-    assert w_enc.shape == (d, d) and w_cls.shape[1] == d and ncls <= 96 and w_val.shape[1] == d and w_val.shape[0] % d == 0
+    cols = enc_chain_class_cols(ncls)
+    assert w_enc.shape == (d, d) and w_cls.shape[1] == d and w_val.shape[1] == d and w_val.shape[0] % d == 0
     nl = w_val.shape[0] // d
     parts, vec = [], []
     if cv2 is not None:
@@ -716,8 +730,8 @@ def pack_enc_chain(d, dtype, w_enc, b_enc, g_enc, be_enc, w_cls, b_cls, w_val, b
         vec += [b2, lw, lb]
     parts.append(chain_pieces(w_val, mem_slots))
     parts.append(chain_pieces(w_enc, mem_slots))
-    wc = torch.zeros(96, d); wc[:ncls] = w_cls
-    bc = torch.zeros(96); bc[:ncls] = b_cls
+    wc = torch.zeros(cols, d); wc[:ncls] = w_cls
+    bc = torch.zeros(cols); bc[:ncls] = b_cls
     parts.append(chain_pieces(wc, perm))
     parts.append(torch.zeros(2 * 2048))
     bv = torch.zeros(6 * d); bv[:nl * d] = b_val
@@ -735,8 +749,9 @@ class EncChainOp:
                  total_rows, ncls, eps_p, eps_e):
         nl = len(values)
         assert stream.dtype == inp.dtype == om.dtype and vec.dtype == torch.float32 and cls_max.dtype == torch.float32
-        assert stream.numel() * 2 == _nat.lib().lwdetr_enc_chain_pieces(d, k5, nl) * 4096, "stream size"
-        assert vec.numel() == _nat.lib().lwdetr_enc_chain_vec_floats(d, k5), "vec size"
+        assert stream.numel() * 2 == _nat.lib().lwdetr_enc_chain_pieces_cls(d, k5, nl, ncls) * 4096, "stream size"
+        assert vec.numel() == _nat.lib().lwdetr_enc_chain_vec_floats_cls(d, k5, ncls), "vec size"
+        assert ld_cls >= _nat.lib().lwdetr_enc_chain_class_cols(ncls) and cls.numel() >= total_rows * ld_cls, "class logits"
         self._vals = (C.c_void_p * nl)(*[v.data_ptr() for v in values])
         self.args = (_ptr(inp), ld_in, k5, _ptr(memory), _ptr(om), _ptr(cls), ld_cls, _ptr(cls_max), self._vals, nl, _ptr(rowvalid),
                      _ptr(notpad), _ptr(stream), _ptr(vec), M, d, npix, S, lsi, total_rows, ncls, float(eps_p), float(eps_e),
