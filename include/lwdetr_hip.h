@@ -279,7 +279,16 @@ int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, const float* b1
  * of the new rows (feature taps), stats_out (optional, (M, 2) f32) mean and 1/sqrt(var + eps_next) of the new rows.
  * wstream / vec: lwdetr_amd.kernels.pack_vit_block (all weights of the block as one stream of 1 KB MFMA fragments in
  * consumption order; f32 vectors b1' | bp | g1 | 1/g1 | b2 | 1/g2 | g2 | bqkv'); sizes from the two helpers below.
- * hd must be a power of two; gamma_1 / gamma_2 must be non-zero (the kernel divides by them in f32). */
+ * hd must be a power of two; gamma_1 / gamma_2 must be non-zero (the kernel divides by them in f32). Refused with BAD_ARG: a row stride
+ * below C (ldx, ldatt, ld2 with out2), a stats_out that is not 4-byte aligned, q_out / k_out / vt_out (M * C elements each) that overlap one
+ * another - lwdetr_vit_qkv and lwdetr_vit_stem refuse the same (ldx, ldpos below C; overlapping outputs).
+ *
+ * Launch-form record of lwdetr_vit_block / lwdetr_vit_qkv / lwdetr_vit_stem: one process-wide host counter per kernel instantiation
+ * (vitblock_<dtype>_c<C>_nh<NH>_wpc<WPC>_qkv<0|1>_g16_<0|1>, vit_qkv_<dtype>_c<C>, vit_stem_<dtype>_c<C>), incremented after a launch was
+ * issued and accepted - a refused request counts nothing. lwdetr_vit_path_counts copies the first min(n, count) counters to out (out may be
+ * NULL) and returns count; lwdetr_vit_path_name(i) names counter i (NULL outside [0, count)). Tests assert which form served a launch. */
+int lwdetr_vit_path_counts(long* out, int n);
+const char* lwdetr_vit_path_name(int i);
 long lwdetr_vit_block_stream_bytes(int C, int has_qkv);
 long lwdetr_vit_block_vec_floats(int C);
 int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, const void* wstream, const float* vec, void* out2,

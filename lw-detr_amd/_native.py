@@ -98,6 +98,9 @@ def lib():
         l.lwdetr_gemm_path_counts.argtypes = [C.POINTER(C.c_long), i]
         l.lwdetr_gemm_path_name.argtypes = [i]
         l.lwdetr_gemm_path_name.restype = C.c_char_p
+        l.lwdetr_vit_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_vit_path_name.argtypes = [i]
+        l.lwdetr_vit_path_name.restype = C.c_char_p
         l.lwdetr_attention_tuning.argtypes = [i]
         l.lwdetr_attention_tuning.restype = None
         l.lwdetr_attention_tuning_cfg.argtypes = [i]
@@ -198,6 +201,15 @@ def gemm_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_gemm_path_counts(buf, n)
     return {l.lwdetr_gemm_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def vit_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_vit_block / lwdetr_vit_qkv / lwdetr_vit_stem in this process (lwdetr_vit_path_counts)."""
+    l = lib()
+    n = l.lwdetr_vit_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_vit_path_counts(buf, n)
+    return {l.lwdetr_vit_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def tuning_set(name: str, value=None):

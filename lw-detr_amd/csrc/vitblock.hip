@@ -24,6 +24,7 @@
 // of the next contraction over its rows, with k-slot (step 2n + beta, half h, s = 4 b' + e) <-> row 32 n + 16 beta + 8 b' +
 // 4 h + e: the host permutes the weight columns accordingly (lwdetr_amd/kernels.py:pack_vit_block).
 #include "common.h"
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -102,6 +103,31 @@ struct VbParams {
     int heads, hd_log2, Tp;
     unsigned qkv_bytes;                // size of each of q / k / vt in bytes (buffer bound)
 };
+
+// ---- launch-form record (lwdetr_vit_path_counts; modelled on lwdetr_gemm_path_counts): one relaxed host counter per kernel instantiation,
+// bumped only when the launch check succeeded. Counters 0 .. 11: vitblock_kernel f16 - form (C = 192 half tile: NH 1 / WPC 2; C = 192: NH 2 / WPC 1;
+// C = 384: NH 1 / WPC 1) x QKV x G16; 12 .. 17: bf16 - form x QKV (no packed-f16 GELU); 18 .. 21: vit_qkv_kernel (dtype, C); 22 .. 25: vit_stem_kernel.
+constexpr int VP_COUNT = 26;
+std::atomic<long> g_vit_path[VP_COUNT];
+const char* const kVitPathNames[VP_COUNT] = {
+    "vitblock_f16_c192_nh1_wpc2_qkv0_g16_0", "vitblock_f16_c192_nh1_wpc2_qkv0_g16_1", "vitblock_f16_c192_nh1_wpc2_qkv1_g16_0", "vitblock_f16_c192_nh1_wpc2_qkv1_g16_1",
+    "vitblock_f16_c192_nh2_wpc1_qkv0_g16_0", "vitblock_f16_c192_nh2_wpc1_qkv0_g16_1", "vitblock_f16_c192_nh2_wpc1_qkv1_g16_0", "vitblock_f16_c192_nh2_wpc1_qkv1_g16_1",
+    "vitblock_f16_c384_nh1_wpc1_qkv0_g16_0", "vitblock_f16_c384_nh1_wpc1_qkv0_g16_1", "vitblock_f16_c384_nh1_wpc1_qkv1_g16_0", "vitblock_f16_c384_nh1_wpc1_qkv1_g16_1",
+    "vitblock_bf16_c192_nh1_wpc2_qkv0_g16_0", "vitblock_bf16_c192_nh1_wpc2_qkv1_g16_0", "vitblock_bf16_c192_nh2_wpc1_qkv0_g16_0", "vitblock_bf16_c192_nh2_wpc1_qkv1_g16_0",
+    "vitblock_bf16_c384_nh1_wpc1_qkv0_g16_0", "vitblock_bf16_c384_nh1_wpc1_qkv1_g16_0",
+    "vit_qkv_f16_c192", "vit_qkv_f16_c384", "vit_qkv_bf16_c192", "vit_qkv_bf16_c384",
+    "vit_stem_f16_c192", "vit_stem_f16_c384", "vit_stem_bf16_c192", "vit_stem_bf16_c384"};
+template <typename T, int C, int NH, bool QKV, int WPC, bool G16> constexpr int vb_path() {
+    static_assert((C == 192 && ((NH == 1 && WPC == 2) || (NH == 2 && WPC == 1))) || (C == 384 && NH == 1 && WPC == 1), "a form the record has no name for");
+    static_assert(!G16 || std::is_same<T, f16>::value, "");
+    constexpr int form = C == 384 ? 2 : (WPC == 2 ? 0 : 1);
+    return std::is_same<T, f16>::value ? form * 4 + (QKV ? 2 : 0) + (G16 ? 1 : 0) : 12 + form * 2 + (QKV ? 1 : 0);
+}
+template <typename T, int C> constexpr int vq_path(int base) { return base + (std::is_same<T, f16>::value ? 0 : 2) + (C == 384 ? 1 : 0); }
+inline int vit_path_done(int path, int rc) {
+    if (rc == LWDETR_OK && path >= 0 && path < VP_COUNT) g_vit_path[path].fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
 
 #define VB_VMW(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 // wait until at most n vector-memory operations of this wave are outstanding (n wave-uniform, rounded down to a multiple of 3)
@@ -1033,7 +1059,7 @@ int launch_vq(const VbParams& p, hipStream_t st) {
     while (((p.M / 8 + grid * 4 - 1) / (grid * 4)) * 8 > 32 * NH) ++grid;
     ProfScope ps(KID_VITBLOCK, 6.0 * p.M * C * C, (double)p.M * C * sizeof(T) * 4, st);
     hipLaunchKernelGGL((vit_qkv_kernel<T, C, NH>), dim3((unsigned)grid), dim3(256), lds, st, p);
-    return lwdetr_check_launch();
+    return vit_path_done(vq_path<T, C>(18), lwdetr_check_launch());
 }
 
 
@@ -1388,7 +1414,7 @@ int launch_vs(const VsParams& p, hipStream_t st) {
     while (((M / 8 + grid * 4 - 1) / (grid * 4)) * 8 > 32 * NH) ++grid;
     ProfScope ps(KID_VITBLOCK, (2.0 * 768 + 6.0 * C) * M * C, (double)M * 768 * sizeof(T) + (double)M * C * sizeof(T) * 5, st);
     hipLaunchKernelGGL((vit_stem_kernel<T, C, NH>), dim3((unsigned)grid), dim3(256), lds, st, p);
-    return lwdetr_check_launch();
+    return vit_path_done(vq_path<T, C>(22), lwdetr_check_launch());
 }
 
 struct VbLaunchState { bool attr_done; int ncu; };
@@ -1425,7 +1451,7 @@ int launch_vb(const VbParams& p, hipStream_t st) {
     ProfScope ps(KID_VITBLOCK, (16.0 + 2.0 + (QKV ? 6.0 : 0.0)) * p.M * C * C,
                  (double)p.M * C * sizeof(T) * 3 + (QKV ? 3.0 : 0.0) * p.M * C * sizeof(T) + (p.out2 ? 1.0 : 0.0) * p.M * C * sizeof(T), st);
     hipLaunchKernelGGL((vitblock_kernel<T, C, NH, QKV, WPC, G16>), dim3((unsigned)grid), dim3(256), lds, st, p);
-    return lwdetr_check_launch();
+    return vit_path_done(vb_path<T, C, NH, QKV, WPC, G16>(), lwdetr_check_launch());
 }
 
 template <typename T>
@@ -1462,6 +1488,19 @@ int dispatch_vb(const VbParams& p, int C, bool qkv, hipStream_t st) {
 
 }  // namespace
 
+extern "C" int lwdetr_vit_path_counts(long* out, int n) {
+    for (int i = 0; out && i < n && i < VP_COUNT; ++i) out[i] = g_vit_path[i].load(std::memory_order_relaxed);
+    return VP_COUNT;
+}
+extern "C" const char* lwdetr_vit_path_name(int i) { return i >= 0 && i < VP_COUNT ? kVitPathNames[i] : nullptr; }
+
+// q / k / v^T are three separate buffers of M * C elements each: the kernels store to all of them from every wave, in no order
+static bool vb_qkv_overlap(const void* q, const void* k, const void* vt, long M, int C) {
+    const uintptr_t n = (uintptr_t)M * (uintptr_t)C * 2u, a = (uintptr_t)q, b = (uintptr_t)k, c = (uintptr_t)vt;
+    auto hit = [n](uintptr_t u, uintptr_t v) { return u < v + n && v < u + n; };
+    return hit(a, b) || hit(a, c) || hit(b, c);
+}
+
 extern "C" long lwdetr_vit_block_stream_bytes(int C, int has_qkv) {
     if (C != 192 && C != 384) return -LWDETR_ERR_UNSUPPORTED;
     const long np = C / 32 + 2 * (C / 8) + (has_qkv ? 3 * (C / 32) : 0);
@@ -1477,6 +1516,8 @@ extern "C" int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, 
     if (ldx % 8 != 0 || ldatt % 8 != 0 || (out2 && ld2 % 8 != 0)) return LWDETR_ERR_BAD_ARG;
     if (M % 8 != 0) return LWDETR_ERR_UNSUPPORTED;        // tokens are dealt to waves in runs of 8 (16-byte V^T stores)
     if (((uintptr_t)wstream | (uintptr_t)vec | (uintptr_t)att) % 16 != 0 || (uintptr_t)x % 16 != 0 || (uintptr_t)out2 % 16 != 0) return LWDETR_ERR_BAD_ARG;
+    // rows narrower than C would overlap (and the last one would end behind the buffer bound of its wave); stats_out is written as floats
+    if (ldx < C || ldatt < C || (out2 && ld2 < C) || (uintptr_t)stats_out % 4 != 0) return LWDETR_ERR_BAD_ARG;
     VbParams p = {};
     p.x = x; p.ldx = ldx; p.att = att; p.ldatt = ldatt; p.wstream = wstream; p.vec = vec; p.out2 = out2; p.ld2 = ld2;
     p.stats_out = stats_out; p.M = M; p.eps = eps; p.eps_next = eps_next; p.qscale = qscale;
@@ -1486,6 +1527,7 @@ extern "C" int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, 
             return LWDETR_ERR_BAD_ARG;
         if (hd < 8 || Tp % 8 != 0) return LWDETR_ERR_UNSUPPORTED;
         if (M % Tp != 0 || (double)M * C * 2.0 >= 2147483000.0) return LWDETR_ERR_UNSUPPORTED;
+        if (vb_qkv_overlap(q_out, k_out, vt_out, M, C)) return LWDETR_ERR_BAD_ARG;
         int l2 = 0; while ((1 << l2) < hd) ++l2;
         p.q = q_out; p.k = k_out; p.vt = vt_out; p.heads = heads; p.hd_log2 = l2; p.Tp = Tp;
         p.qkv_bytes = (unsigned)((unsigned long)M * C * 2ul);
@@ -1510,6 +1552,7 @@ extern "C" int lwdetr_vit_qkv(const void* x, long ldx, const void* wstream, cons
     if (ldx % 8 != 0 || ((uintptr_t)x | (uintptr_t)wstream | (uintptr_t)vec | (uintptr_t)q_out | (uintptr_t)k_out | (uintptr_t)vt_out) % 16 != 0) return LWDETR_ERR_BAD_ARG;
     if (heads <= 0 || hd < 8 || (hd & (hd - 1)) != 0 || heads * hd != C || Tp <= 0 || Tp % 8 != 0) return LWDETR_ERR_UNSUPPORTED;
     if (M % 8 != 0 || M % Tp != 0 || (double)M * C * 2.0 >= 2147483000.0 || (double)ldx * 64 * 2 >= 2147483000.0) return LWDETR_ERR_UNSUPPORTED;
+    if (ldx < C || vb_qkv_overlap(q_out, k_out, vt_out, M, C)) return LWDETR_ERR_BAD_ARG;
     VbParams p = {};
     p.x = (void*)x; p.ldx = ldx; p.wstream = wstream; p.vec = vec; p.M = M; p.eps_next = eps; p.qscale = qscale;
     int l2 = 0; while ((1 << l2) < hd) ++l2;
@@ -1538,6 +1581,7 @@ extern "C" int lwdetr_vit_stem(const void* img, int B, int img_h, int img_w, int
     if ((double)M * C * 2.0 >= 2147483000.0 || (double)ldx * 64 * 2 >= 2147483000.0 || (double)B * 3 * img_h * img_w * 2.0 >= 2147483000.0 ||
         (double)Tp * ldpos * 2.0 >= 2147483000.0)
         return LWDETR_ERR_UNSUPPORTED;
+    if (ldx < C || ldpos < C || vb_qkv_overlap(q_out, k_out, vt_out, M, C)) return LWDETR_ERR_BAD_ARG;
     VsParams p = {};
     p.img = img; p.img_bytes = (unsigned)((unsigned long)B * 3ul * img_h * img_w * 2ul); p.img_h = img_h; p.img_w = img_w;
     p.Hp = Hp; p.Wp = Wp; p.Twp = Twp; p.pos = pos; p.ldpos = ldpos;

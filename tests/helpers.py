@@ -182,3 +182,22 @@ def served_by(family, launches=1):
         assert set(delta) == {family}, f"expected launches of {family} only, the launches went to {delta}"
     else:
         assert delta == {family: launches}, f"expected {launches} launch(es) of {family}, the launches went to {delta}"
+
+
+@contextlib.contextmanager
+def vit_served_by(form, launches=1):
+    """As served_by for the record of vitblock.hip (lwdetr_vit_path_counts): the lwdetr_vit_block / lwdetr_vit_qkv / lwdetr_vit_stem launches inside
+    the block went to exactly the instantiation `form` (a name of lwdetr_vit_path_name: "vitblock_f16_c192_nh1_wpc2_qkv1_g16_1", "vit_qkv_bf16_c384",
+    ...), `launches` times (None: at least once), and to no other."""
+    import torch
+    from lwdetr_amd import _native
+    before = _native.vit_path_counts()
+    assert form in before, f"unknown ViT kernel form {form!r}: {sorted(before)}"
+    yield
+    torch.cuda.synchronize()
+    after = _native.vit_path_counts()
+    delta = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+    if launches is None:
+        assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
+    else:
+        assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"

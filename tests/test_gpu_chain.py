@@ -173,7 +173,9 @@ def test_vit_qkv_matches_torch(dtype, c, heads, m, tp):
     q = torch.full((nb, heads, tp, hd), float("nan"), dtype=dtype, device=DEV)
     k = torch.full_like(q, float("nan"))
     vt = torch.full((nb, heads, hd, tp), float("nan"), dtype=dtype, device=DEV)
-    K.VitQkvOp(x.to(DEV), stream.to(DEV), vec.to(DEV), m, c, 1e-6, q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd, Tp=tp)()
+    from tests.helpers import vit_served_by
+    with vit_served_by(f"vit_qkv_{'f16' if dtype == torch.float16 else 'bf16'}_c{c}"):     # (element-wise checks at edge shapes: test_gpu_vitblock.py)
+        K.VitQkvOp(x.to(DEV), stream.to(DEV), vec.to(DEV), m, c, 1e-6, q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd, Tp=tp)()
     torch.cuda.synchronize()
     xn = torch.nn.functional.layer_norm(x.float(), (c,), lw, lb, 1e-6)
     ref = xn @ wqkv.t() + torch.cat([qb, torch.zeros(c), vb])
@@ -210,7 +212,9 @@ def test_vit_stem_matches_torch(dtype, c, heads, b, hp, twp):
     k = torch.full_like(q, float("nan"))
     vt = torch.full((b, heads, hd, tp), float("nan"), dtype=dtype, device=DEV)
     op = K.VitStemOp(img.to(DEV), pos.to(DEV), x, stream.to(DEV), vec.to(DEV), b, hp, hp, twp, c, 1e-6, q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd)
-    op()
+    from tests.helpers import vit_served_by
+    with vit_served_by(f"vit_stem_{'f16' if dtype == torch.float16 else 'bf16'}_c{c}"):    # (pad rows and edge geometries: test_gpu_vitblock.py)
+        op()
     torch.cuda.synchronize()
     wd = wpe.to(dtype).float()
     y = torch.nn.functional.conv2d(img.float(), wd, bpe, stride=16).permute(0, 2, 3, 1)                  # (b, hp, hp, c) raster

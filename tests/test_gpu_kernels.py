@@ -898,6 +898,7 @@ def test_vit_block(dtype, c, heads, m, tp, half, gelu16, monkeypatch, knobs):
     same 16-bit weights. 51200 = BASELINE config 2 (32 images x 1600 tokens: 50 tokens per wave), 64000 / 25600 = more than one
     round of workgroups, 12816 / 13000 / 20000 = ragged token counts per wave and tiles that straddle images."""
     from lwdetr_amd import kernels as K
+    from tests.helpers import vit_served_by
     if c != 192 and half == "1":
         pytest.skip("the half-tile form exists for C = 192 only")
     if gelu16 == "1" and dtype != torch.float16:
@@ -937,7 +938,10 @@ def test_vit_block(dtype, c, heads, m, tp, half, gelu16, monkeypatch, knobs):
             k = torch.full_like(q, float("nan"))
             vt = torch.full((nb, heads, hd, tp), float("nan"), dtype=dtype, device=_dev())
             kw = dict(q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd, Tp=tp)
-        K.VitBlockOp(xx, att, stream, vec, m, c, 1e-6, out2=out2[:, c:], ld2=2 * c, stats_out=stats, eps_next=1e-6, **kw)()
+        nh_wpc = "nh1_wpc2" if (c == 192 and half == "1") else ("nh2_wpc1" if c == 192 else "nh1_wpc1")
+        form = f"vitblock_{'f16' if dtype == torch.float16 else 'bf16'}_c{c}_{nh_wpc}_qkv{int(with_qkv)}_g16_{int(gelu16 == '1' and dtype == torch.float16)}"
+        with vit_served_by(form):          # the one instantiation this case means to test (element-wise checks at edge shapes: test_gpu_vitblock.py)
+            K.VitBlockOp(xx, att, stream, vec, m, c, 1e-6, out2=out2[:, c:], ld2=2 * c, stats_out=stats, eps_next=1e-6, **kw)()
         torch.cuda.synchronize()
         assert torch.isfinite(xx.float()).all()
         assert _relerr(xx, ref) < tol, _relerr(xx, ref)
@@ -997,7 +1001,9 @@ def test_vit_block_rounding_points_fp64(gelu, monkeypatch, knobs):
     hid = r16(torch.from_numpy(gelu_vb16(hid.cpu().numpy())).to(_dev()).float())
     ref = r16((x1 + g2.float().double() * (hid @ w216.t() + b2.float().double())).float())
     xx = x.to(dtype).clone()
-    K.VitBlockOp(xx, att.to(dtype), stream.to(_dev()), vec.to(_dev()), m, c, 1e-6)()
+    from tests.helpers import vit_served_by
+    with vit_served_by(f"vitblock_f16_c192_nh1_wpc2_qkv0_g16_{int(gelu == 'packed_f16')}"):       # M = 12800 on 256 CUs: the half-tile form
+        K.VitBlockOp(xx, att.to(dtype), stream.to(_dev()), vec.to(_dev()), m, c, 1e-6)()
     d = (xx.double() - ref).abs()
     # one f16 ulp of the result at most on a few elements (f32 vs f64 accumulation order), far below 1e-3 relative on average
     k_ = 1 if gelu == "f32" else 3
