@@ -42,7 +42,12 @@ extern "C" {
 #define LWDETR_ERR_LAUNCH (-3)
 
 /* out[b,q,m*D+c] = sum_l sum_p attn[b,q,m,l,p] * bilinear(value[b, lvl l, :, m, c], (loc_x*W_l-.5, loc_y*H_l-.5)), zero pad.
- * value (B,S,M,D); shapes (L,2) int64 (H,W); level_start (L) int64; loc (B,Q,M,L,P,2) (x,y); attn (B,Q,M,L,P); out (B,Q,M*D). */
+ * value (B,S,M,D); shapes (L,2) int64 (H,W); level_start (L) int64; loc (B,Q,M,L,P,2) (x,y); attn (B,Q,M,L,P); out (B,Q,M*D).
+ * A sample contributes iff h_im > -1 && w_im > -1 && h_im < H && w_im < W (h_im = loc_y*H - .5, w_im = loc_x*W - .5): a sample with a
+ * non-finite location contributes nothing. value must be finite: the vector kernel reads a clamped in-map pixel with weight 0 for a
+ * corner outside the map, so an inf / NaN in value reaches queries that do not sample it. The vector kernel (D % 8 == 0, P <= 8,
+ * dtype 0 ... 2) serves a call only when value and out are aligned to 8 elements; any other call goes to the one-thread-per-element
+ * kernel. */
 int lwdetr_msda_forward(const void* value, const int64_t* shapes, const int64_t* level_start, const void* loc,
                         const void* attn, void* out, int B, int S, int M, int D, int L, int Q, int P, int dtype,
                         void* hip_stream);
@@ -57,7 +62,10 @@ int lwdetr_msda_backward(const void* value, const int64_t* shapes, const int64_t
 
 /* Model-path variant: oa is the (B*Q, ld_oa) output of the fused sampling_offsets|attention_weights Linear
  * (offsets at column 0: M*L*P*2 values, logits at column logit_col: M*L*P values); ref_boxes (B,Q,4) f32 (cx,cy,w,h);
- * valid_ratios (B,L,2) f32 (w,h). Computes softmax over L*P and loc = ref_xy + off / P * ref_wh * 0.5 in-kernel. D % 8 == 0. */
+ * valid_ratios (B,L,2) f32 (w,h). Computes the softmax over the L*P logits of a (row, head) and, per level l with vr = valid_ratios[b,l],
+ * loc = ref_xy*vr + off / P * (ref_wh*vr) * 0.5 in-kernel (f32), then samples as lwdetr_msda_forward does (a non-finite location contributes
+ * nothing; value must be finite). (L, P) in {1,2} x {2,4}, D % 8 == 0, dtype 0 ... 2. LWDETR_ERR_BAD_ARG unless 0 <= 2*M*L*P <= logit_col,
+ * logit_col + M*L*P <= ld_oa, and value and out are aligned to 8 elements. */
 int lwdetr_msda_fused_forward(const void* value, const int64_t* shapes, const int64_t* level_start, const void* oa,
                               long ld_oa, int logit_col, const float* ref_boxes, const float* valid_ratios, void* out,
                               int B, int S, int M, int D, int L, int Q, int P, int dtype, void* hip_stream);
@@ -289,6 +297,12 @@ int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, const float* b1
  * NULL) and returns count; lwdetr_vit_path_name(i) names counter i (NULL outside [0, count)). Tests assert which form served a launch. */
 int lwdetr_vit_path_counts(long* out, int n);
 const char* lwdetr_vit_path_name(int i);
+
+/* The same record for msda.hip: one counter per kernel instantiation that lwdetr_msda_forward / lwdetr_msda_backward / lwdetr_msda_fused_forward
+ * launch - msda_vec8_{f32,f16,bf16}_p{2,4,n} (n: run-time P), msda_generic_{f32,f16,bf16,f64}, msda_fused_{f32,f16,bf16}_l{1,2}p{2,4},
+ * msda_backward_{f32,f64}. */
+int lwdetr_msda_path_counts(long* out, int n);
+const char* lwdetr_msda_path_name(int i);
 long lwdetr_vit_block_stream_bytes(int C, int has_qkv);
 long lwdetr_vit_block_vec_floats(int C);
 int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, const void* wstream, const float* vec, void* out2,

@@ -101,6 +101,9 @@ def lib():
         l.lwdetr_vit_path_counts.argtypes = [C.POINTER(C.c_long), i]
         l.lwdetr_vit_path_name.argtypes = [i]
         l.lwdetr_vit_path_name.restype = C.c_char_p
+        l.lwdetr_msda_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_msda_path_name.argtypes = [i]
+        l.lwdetr_msda_path_name.restype = C.c_char_p
         l.lwdetr_attention_tuning.argtypes = [i]
         l.lwdetr_attention_tuning.restype = None
         l.lwdetr_attention_tuning_cfg.argtypes = [i]
@@ -210,6 +213,15 @@ def vit_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_vit_path_counts(buf, n)
     return {l.lwdetr_vit_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def msda_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_msda_forward / lwdetr_msda_backward / lwdetr_msda_fused_forward in this process (lwdetr_msda_path_counts)."""
+    l = lib()
+    n = l.lwdetr_msda_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_msda_path_counts(buf, n)
+    return {l.lwdetr_msda_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def tuning_set(name: str, value=None):

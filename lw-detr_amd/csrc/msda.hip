@@ -13,7 +13,37 @@
 //                     boxes, and does softmax + location arithmetic (ms_deform_attn.py:117-131) in the prologue.
 #include "common.h"
 
+#include <atomic>
+#include <type_traits>
+
 namespace {
+
+// ---- launch-form record (lwdetr_msda_path_counts; modelled on lwdetr_vit_path_counts): one relaxed host counter per kernel instantiation, bumped
+// only when the launch check succeeded. Counters 0 .. 8: msda_vec8_kernel (dtype x P form 2 / 4 / run-time); 9 .. 12: msda_generic_kernel;
+// 13 .. 24: msda_fused_kernel (dtype x (L, P)); 25, 26: msda_backward_kernel.
+constexpr int MP_COUNT = 27;
+std::atomic<long> g_msda_path[MP_COUNT];
+const char* const kMsdaPathNames[MP_COUNT] = {
+    "msda_vec8_f32_p2", "msda_vec8_f32_p4", "msda_vec8_f32_pn", "msda_vec8_f16_p2", "msda_vec8_f16_p4", "msda_vec8_f16_pn",
+    "msda_vec8_bf16_p2", "msda_vec8_bf16_p4", "msda_vec8_bf16_pn",
+    "msda_generic_f32", "msda_generic_f16", "msda_generic_bf16", "msda_generic_f64",
+    "msda_fused_f32_l1p2", "msda_fused_f32_l1p4", "msda_fused_f32_l2p2", "msda_fused_f32_l2p4",
+    "msda_fused_f16_l1p2", "msda_fused_f16_l1p4", "msda_fused_f16_l2p2", "msda_fused_f16_l2p4",
+    "msda_fused_bf16_l1p2", "msda_fused_bf16_l1p4", "msda_fused_bf16_l2p2", "msda_fused_bf16_l2p4",
+    "msda_backward_f32", "msda_backward_f64"};
+template <typename T> constexpr int mp_dtype() {       // f32, f16, bf16, f64: the order of the names
+    return std::is_same<T, float>::value ? 0 : std::is_same<T, f16>::value ? 1 : std::is_same<T, bf16>::value ? 2 : 3;
+}
+template <typename T, int TP> constexpr int mp_vec8() { return mp_dtype<T>() * 3 + (TP == 2 ? 0 : TP == 4 ? 1 : 2); }
+template <typename T> constexpr int mp_generic() { return 9 + mp_dtype<T>(); }
+template <typename T, int TL, int TP> constexpr int mp_fused() { return 13 + mp_dtype<T>() * 4 + (TL - 1) * 2 + (TP == 2 ? 0 : 1); }
+template <typename T> constexpr int mp_backward() { return std::is_same<T, float>::value ? 25 : 26; }
+inline int msda_path_done(int path, int rc) {
+    if (rc == LWDETR_OK && path >= 0 && path < MP_COUNT) g_msda_path[path].fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
+// the vector kernels read value and write out in 8-element pieces
+template <typename T> inline bool aligned8(const void* p) { return (uintptr_t)p % (8 * sizeof(T)) == 0; }
 
 struct MsdaParams {
     const void* value; const int64_t* shapes; const int64_t* lsi; const void* loc; const void* aw; void* out;
@@ -70,16 +100,20 @@ template <typename T> struct Chan8 {          // 8 consecutive channels of one p
 };
 
 // One sampling point: 4 corner offsets (in elements, already clamped in-bounds) + 4 corner weights
-// (zeroed for corners / samples outside the map; weight already multiplied by the attention weight).
+// (zeroed for corners / samples outside the map; weight already multiplied by the attention weight). A sample that is not `inside` - a
+// non-finite location among them - is moved to h_im = w_im = 0 before anything is computed from it, so hh / hw are finite and its zeroed
+// attention weight gives four zero weights (no NaN * 0). Of the ways to do this, this one leaves registers and time per launch nearest to
+// the multiply-by-zeroed-weight form it replaces (profiles/r8b_msda_fp64_worst_ratios.txt).
 struct Corners { long o[4]; float w[4]; };
 
 __device__ __forceinline__ Corners make_corners(float loc_x, float loc_y, float attn, int H, int W, long ws) {
     Corners c;
-    const float h_im = loc_y * H - 0.5f, w_im = loc_x * W - 0.5f;
-    const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
+    const float h_raw = loc_y * H - 0.5f, w_raw = loc_x * W - 0.5f;
+    const bool inside = h_raw > -1.f && w_raw > -1.f && h_raw < (float)H && w_raw < (float)W;
+    const float h_im = inside ? h_raw : 0.f, w_im = inside ? w_raw : 0.f;
     const float hf = floorf(h_im), wf = floorf(w_im);
     const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-    int hl = inside ? (int)hf : 0, wl = inside ? (int)wf : 0;
+    const int hl = (int)hf, wl = (int)wf;
     const int hh_i = hl + 1, wh_i = wl + 1;
     const bool t = hl >= 0, l = wl >= 0, bo = hh_i <= H - 1, r = wh_i <= W - 1;
     const int h0 = t ? hl : 0, w0 = l ? wl : 0, h1 = bo ? hh_i : H - 1, w1 = r ? wh_i : W - 1;
@@ -220,18 +254,20 @@ template <typename T> int launch_plain(MsdaParams p, hipStream_t st) {
     const long n = (long)p.B * p.Q * p.M * p.D;
     if (n == 0) return LWDETR_OK;
     const double bytes = ((double)p.B * p.S * p.M * p.D + (double)p.B * p.Q * p.M * p.L * p.P * 3 + (double)n) * sizeof(T);
-    if (p.D % 8 == 0 && p.P <= MAX_P && sizeof(T) <= 4) {
+    int path;
+    if (p.D % 8 == 0 && p.P <= MAX_P && sizeof(T) <= 4 && aligned8<T>(p.value) && aligned8<T>(p.out)) {
         dim3 grid; fill_grid(p, grid);
         ProfScope ps(KID_MSDA, 0.0, bytes, st);
-        if (p.P == 2) hipLaunchKernelGGL((msda_vec8_kernel<T, 2>), grid, dim3(256), 0, st, p);
-        else if (p.P == 4) hipLaunchKernelGGL((msda_vec8_kernel<T, 4>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((msda_vec8_kernel<T, 0>), grid, dim3(256), 0, st, p);
+        if (p.P == 2) { path = mp_vec8<T, 2>(); hipLaunchKernelGGL((msda_vec8_kernel<T, 2>), grid, dim3(256), 0, st, p); }
+        else if (p.P == 4) { path = mp_vec8<T, 4>(); hipLaunchKernelGGL((msda_vec8_kernel<T, 4>), grid, dim3(256), 0, st, p); }
+        else { path = mp_vec8<T, 0>(); hipLaunchKernelGGL((msda_vec8_kernel<T, 0>), grid, dim3(256), 0, st, p); }
     } else {
         long blocks = (n + 255) / 256; if (blocks > 65535 * 16) blocks = 65535 * 16;
         ProfScope ps(KID_MSDA_GENERIC, 0.0, bytes, st);
+        path = mp_generic<T>();
         hipLaunchKernelGGL((msda_generic_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, p);
     }
-    return lwdetr_check_launch();
+    return msda_path_done(path, lwdetr_check_launch());
 }
 
 template <> int launch_plain<double>(MsdaParams p, hipStream_t st) {
@@ -240,20 +276,24 @@ template <> int launch_plain<double>(MsdaParams p, hipStream_t st) {
     long blocks = (n + 255) / 256; if (blocks > 65535 * 16) blocks = 65535 * 16;
     ProfScope ps(KID_MSDA_GENERIC, 0.0, 0.0, st);
     hipLaunchKernelGGL((msda_generic_kernel<double>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    return lwdetr_check_launch();
+    return msda_path_done(mp_generic<double>(), lwdetr_check_launch());
 }
 
 template <typename T> int launch_fused(MsdaParams p, hipStream_t st) {
     dim3 grid; fill_grid(p, grid);
     const double bytes = ((double)p.B * p.S * p.M * p.D + (double)p.B * p.Q * p.M * p.L * p.P * 3 +
                           (double)p.B * p.Q * p.M * p.D) * sizeof(T);
+    if (!((p.L == 1 || p.L == 2) && (p.P == 2 || p.P == 4))) return LWDETR_ERR_UNSUPPORTED;
+    const long mlp = (long)p.M * p.L * p.P;              // the offsets fill columns [0, 2 mlp) of an oa row, the logits [logit_col, logit_col + mlp)
+    if (p.oa_logit_off < 0 || p.ld_oa < 0 || p.oa_logit_off < 2 * mlp || p.ld_oa < p.oa_logit_off + mlp) return LWDETR_ERR_BAD_ARG;
+    if (!aligned8<T>(p.value) || !aligned8<T>(p.out)) return LWDETR_ERR_BAD_ARG;
     ProfScope ps(KID_MSDA_FUSED, 0.0, bytes, st);
-    if (p.L == 1 && p.P == 2) hipLaunchKernelGGL((msda_fused_kernel<T, 1, 2>), grid, dim3(256), 0, st, p);
-    else if (p.L == 2 && p.P == 4) hipLaunchKernelGGL((msda_fused_kernel<T, 2, 4>), grid, dim3(256), 0, st, p);
-    else if (p.L == 1 && p.P == 4) hipLaunchKernelGGL((msda_fused_kernel<T, 1, 4>), grid, dim3(256), 0, st, p);
-    else if (p.L == 2 && p.P == 2) hipLaunchKernelGGL((msda_fused_kernel<T, 2, 2>), grid, dim3(256), 0, st, p);
-    else return LWDETR_ERR_UNSUPPORTED;
-    return lwdetr_check_launch();
+    int path;
+    if (p.L == 1 && p.P == 2) { path = mp_fused<T, 1, 2>(); hipLaunchKernelGGL((msda_fused_kernel<T, 1, 2>), grid, dim3(256), 0, st, p); }
+    else if (p.L == 2 && p.P == 4) { path = mp_fused<T, 2, 4>(); hipLaunchKernelGGL((msda_fused_kernel<T, 2, 4>), grid, dim3(256), 0, st, p); }
+    else if (p.L == 1 && p.P == 4) { path = mp_fused<T, 1, 4>(); hipLaunchKernelGGL((msda_fused_kernel<T, 1, 4>), grid, dim3(256), 0, st, p); }
+    else { path = mp_fused<T, 2, 2>(); hipLaunchKernelGGL((msda_fused_kernel<T, 2, 2>), grid, dim3(256), 0, st, p); }
+    return msda_path_done(path, lwdetr_check_launch());
 }
 
 // --------------------------------------------------------------------------------------------- backward
@@ -323,7 +363,7 @@ template <typename T> int launch_backward(MsdaParams p, const void* grad_out, vo
     ProfScope ps(KID_MSDA_GENERIC, 0.0, 0.0, st);
     hipLaunchKernelGGL((msda_backward_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, p, (const T*)grad_out, (T*)grad_value,
                        (T*)grad_loc, (T*)grad_aw, gs);
-    return lwdetr_check_launch();
+    return msda_path_done(mp_backward<T>(), lwdetr_check_launch());
 }
 
 }  // namespace
@@ -383,5 +423,11 @@ int lwdetr_msda_fused_forward(const void* value, const int64_t* shapes, const in
         default: return LWDETR_ERR_UNSUPPORTED;
     }
 }
+
+int lwdetr_msda_path_counts(long* out, int n) {
+    for (int i = 0; out && i < n && i < MP_COUNT; ++i) out[i] = g_msda_path[i].load(std::memory_order_relaxed);
+    return MP_COUNT;
+}
+const char* lwdetr_msda_path_name(int i) { return i >= 0 && i < MP_COUNT ? kMsdaPathNames[i] : nullptr; }
 
 }  // extern "C"

@@ -201,3 +201,22 @@ def vit_served_by(form, launches=1):
         assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
     else:
         assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"
+
+
+@contextlib.contextmanager
+def msda_served_by(form, launches=1):
+    """As served_by for the record of msda.hip (lwdetr_msda_path_counts): the lwdetr_msda_forward / lwdetr_msda_backward / lwdetr_msda_fused_forward
+    launches inside the block went to exactly the instantiation `form` (a name of lwdetr_msda_path_name: "msda_vec8_f16_pn", "msda_generic_f64",
+    "msda_fused_bf16_l2p4", "msda_backward_f32", ...), `launches` times (None: at least once), and to no other."""
+    import torch
+    from lwdetr_amd import _native
+    before = _native.msda_path_counts()
+    assert form in before, f"unknown deformable-attention kernel form {form!r}: {sorted(before)}"
+    yield
+    torch.cuda.synchronize()
+    after = _native.msda_path_counts()
+    delta = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+    if launches is None:
+        assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
+    else:
+        assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"
