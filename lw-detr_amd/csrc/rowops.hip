@@ -2,6 +2,7 @@
 // with a two-pass (mean, then centred variance) formulation over register-resident values - the same arithmetic as
 // nn.LayerNorm / the projector's channel LayerNorm (biased variance; reference models/backbone/projector.py:43-46).
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -286,43 +287,89 @@ extern "C" int lwdetr_ffn_finish(const void* x, long ldx, const float* partial, 
 //   box_reparam     : final boxes of all decoder layers (models/lwdetr.py:150-155)
 namespace {
 
-template <typename T>
+// select_gather and decoder_inputs give one wave to a row, four rows to a workgroup. VEC: the row bases of the T operands are 16-byte
+// aligned and the row lengths whole 16-byte chunks, so the rows move as 16-byte vectors; otherwise element by element.
+constexpr int GLUE_ROWS = 4;
+
+template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void select_gather_kernel(const T* __restrict__ om, const T* __restrict__ enc_cls, long ldc,
                                                             const float* __restrict__ props, const int64_t* __restrict__ idx,
                                                             T* __restrict__ om_sel, T* __restrict__ logits_out,
-                                                            float* __restrict__ props_sel, int B, int S, int d, int nq, int ncls) {
-    const long row = blockIdx.x;                       // b * nq + q
+                                                            float* __restrict__ props_sel, long rows, int S, int d, int nq, int ncls) {
+    typedef typename Vec<T>::v8 V8;
+    typedef typename Vec<T>::v4 V4;
+    typedef typename std::conditional<sizeof(T) == 2, V8, V4>::type V;
+    constexpr int EPV = 16 / (int)sizeof(T);
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * GLUE_ROWS + (threadIdx.x >> 6);                       // b * nq + q
+    if (row >= rows) return;
     const int b = (int)(row / nq);
     const long src = (long)b * S + idx[row];
-    for (int c = threadIdx.x; c < d; c += blockDim.x) om_sel[row * d + c] = om[src * d + c];
-    for (int c = threadIdx.x; c < ncls; c += blockDim.x) logits_out[row * ncls + c] = enc_cls[src * ldc + c];
-    if (threadIdx.x < 4) props_sel[row * 4 + threadIdx.x] = props[src * 4 + threadIdx.x];
+    if (VEC) {
+        const V* __restrict__ sv = (const V*)(om + src * d);
+        V* __restrict__ ov = (V*)(om_sel + row * d);
+        for (int c = lane; c < d / EPV; c += 64) ov[c] = sv[c];
+    } else {
+        for (int c = lane; c < d; c += 64) om_sel[row * d + c] = om[src * d + c];
+    }
+    for (int c = lane; c < ncls; c += 64) logits_out[row * ncls + c] = enc_cls[src * ldc + c];   // ncls-long rows (91: 182 bytes) start anywhere
+    if (lane < 4) props_sel[row * 4 + lane] = props[src * 4 + lane];
 }
 
-template <typename T>
+template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void decoder_inputs_kernel(const T* __restrict__ enc_delta, const float* __restrict__ props_sel,
                                                              const float* __restrict__ refpoint, const float* __restrict__ vr,
                                                              int L, const T* __restrict__ query_feat,
                                                              const float* __restrict__ dim_t, T* __restrict__ enc_boxes,
                                                              float* __restrict__ ref_out, T* __restrict__ sine,
-                                                             T* __restrict__ xdec, int B, int nq, int d) {
-    const long row = blockIdx.x;
+                                                             T* __restrict__ xdec, long rows, int nq, int d) {
+    typedef typename Vec<T>::v8 V8;
+    typedef typename Vec<T>::v4 V4;
+    typedef typename std::conditional<sizeof(T) == 2, V8, V4>::type V;
+    constexpr int EPV = 16 / (int)sizeof(T);
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * GLUE_ROWS + (threadIdx.x >> 6);
+    if (row >= rows) return;
     const int b = (int)(row / nq), q = (int)(row - (long)b * nq);
     float dl[4], pr[4], ts[4], rp[4], rf[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { dl[i] = to_f32<T>(enc_delta[row * 4 + i]); pr[i] = props_sel[row * 4 + i]; rp[i] = refpoint[q * 4 + i]; }
     ts[0] = dl[0] * pr[2] + pr[0]; ts[1] = dl[1] * pr[3] + pr[1]; ts[2] = expf(dl[2]) * pr[2]; ts[3] = expf(dl[3]) * pr[3];
     rf[0] = rp[0] * ts[2] + ts[0]; rf[1] = rp[1] * ts[3] + ts[1]; rf[2] = expf(rp[2]) * ts[2]; rf[3] = expf(rp[3]) * ts[3];
-    if (threadIdx.x < 4) { enc_boxes[row * 4 + threadIdx.x] = from_f32<T>(ts[threadIdx.x]); ref_out[row * 4 + threadIdx.x] = rf[threadIdx.x]; }
-    const float vx = vr[(long)b * L * 2], vy = vr[(long)b * L * 2 + 1];
-    const float pos[4] = {rf[1] * vy, rf[0] * vx, rf[2] * vx, rf[3] * vy};      // order (y, x, w, h)
-    const int half = d / 2;
-    for (int c = threadIdx.x; c < 2 * d; c += blockDim.x) {
-        const int k = c / half, i = c - k * half;
-        const float e = pos[k] * 6.283185307179586f / dim_t[i];
-        sine[row * 2 * d + c] = from_f32<T>((i & 1) ? __cosf(e) : __sinf(e));   // |e| <= a few 2 pi: v_sin/v_cos, ~1e-6 abs
+    if (lane < 4) {
+        const float t = lane == 0 ? ts[0] : lane == 1 ? ts[1] : lane == 2 ? ts[2] : ts[3];
+        const float r = lane == 0 ? rf[0] : lane == 1 ? rf[1] : lane == 2 ? rf[2] : rf[3];
+        enc_boxes[row * 4 + lane] = from_f32<T>(t);
+        ref_out[row * 4 + lane] = r;
     }
-    for (int c = threadIdx.x; c < d; c += blockDim.x) xdec[row * d + c] = query_feat[(long)q * d + c];
+    const float vx = vr[(long)b * L * 2], vy = vr[(long)b * L * 2 + 1];
+    const float p0 = rf[1] * vy, p1 = rf[0] * vx, p2 = rf[2] * vx, p3 = rf[3] * vy;             // order (y, x, w, h)
+    const int half = d / 2;
+    if (VEC) {          // half is a whole number of chunks: a chunk lies in one of the four blocks and starts at an even column
+        V* __restrict__ sv = (V*)(sine + row * 2 * d);
+        for (int ch = lane; ch < 2 * d / EPV; ch += 64) {
+            const int c0 = ch * EPV, k = c0 / half, i0 = c0 - k * half;
+            const float pk = k == 0 ? p0 : k == 1 ? p1 : k == 2 ? p2 : p3;
+            V o;
+#pragma unroll
+            for (int u = 0; u < EPV; ++u) {
+                const float e = pk * 6.283185307179586f / dim_t[i0 + u];
+                o[u] = from_f32<T>((u & 1) ? __cosf(e) : __sinf(e));   // |e| <= a few 2 pi: v_sin/v_cos, ~1e-6 abs
+            }
+            sv[ch] = o;
+        }
+        const V* __restrict__ qv = (const V*)(query_feat + (long)q * d);
+        V* __restrict__ xv = (V*)(xdec + row * d);
+        for (int c = lane; c < d / EPV; c += 64) xv[c] = qv[c];
+    } else {
+        for (int c = lane; c < 2 * d; c += 64) {
+            const int k = c / half, i = c - k * half;
+            const float pk = k == 0 ? p0 : k == 1 ? p1 : k == 2 ? p2 : p3;
+            const float e = pk * 6.283185307179586f / dim_t[i];
+            sine[row * 2 * d + c] = from_f32<T>((i & 1) ? __cosf(e) : __sinf(e));
+        }
+        for (int c = lane; c < d; c += 64) xdec[row * d + c] = query_feat[(long)q * d + c];
+    }
 }
 
 template <typename T>
@@ -381,9 +428,15 @@ extern "C" int lwdetr_select_gather(const void* om, const void* enc_cls, long ld
         d <= 0 || ncls <= 0 || ldc < ncls) return LWDETR_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)hip_stream;
     ProfScope ps(KID_ELTWISE, 0.0, 2.0 * B * nq * (d + ncls) * 2, st);
-    LWDETR_DISPATCH_T(dtype, hipLaunchKernelGGL((select_gather_kernel<TT>), dim3(B * nq), dim3(256), 0, st, (const TT*)om,
-                                                (const TT*)enc_cls, ldc, props, idx, (TT*)om_sel, (TT*)logits_out, props_sel, B,
-                                                S, d, nq, ncls));
+    const long rows = (long)B * nq;
+    const dim3 grid((unsigned)((rows + GLUE_ROWS - 1) / GLUE_ROWS));
+    const int epv = dtype == DT_F32 ? 4 : 8;
+    const bool vec = d % epv == 0 && !(((uintptr_t)om | (uintptr_t)om_sel) & 15);
+#define GLUE_LAUNCH(VEC)                                                                                                          \
+    hipLaunchKernelGGL((select_gather_kernel<TT, VEC>), grid, dim3(64 * GLUE_ROWS), 0, st, (const TT*)om, (const TT*)enc_cls, ldc, \
+                       props, idx, (TT*)om_sel, (TT*)logits_out, props_sel, rows, S, d, nq, ncls)
+    LWDETR_DISPATCH_T(dtype, { if (vec) GLUE_LAUNCH(true); else GLUE_LAUNCH(false); });
+#undef GLUE_LAUNCH
     return lwdetr_check_launch();
 }
 
@@ -394,9 +447,16 @@ extern "C" int lwdetr_decoder_inputs(const void* enc_delta, const float* props_s
         !sine_out || !xdec_out || B <= 0 || nq <= 0 || d <= 0 || d % 2 || L <= 0) return LWDETR_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)hip_stream;
     ProfScope ps(KID_ELTWISE, 0.0, 3.0 * B * nq * d * 2, st);
-    LWDETR_DISPATCH_T(dtype, hipLaunchKernelGGL((decoder_inputs_kernel<TT>), dim3(B * nq), dim3(256), 0, st, (const TT*)enc_delta,
-                                                props_sel, refpoint, valid_ratios, L, (const TT*)query_feat, dim_t,
-                                                (TT*)enc_boxes_out, ref_out, (TT*)sine_out, (TT*)xdec_out, B, nq, d));
+    const long rows = (long)B * nq;
+    const dim3 grid((unsigned)((rows + GLUE_ROWS - 1) / GLUE_ROWS));
+    const int epv = dtype == DT_F32 ? 4 : 8;
+    const bool vec = (d / 2) % epv == 0 && !(((uintptr_t)query_feat | (uintptr_t)sine_out | (uintptr_t)xdec_out) & 15);
+#define GLUE_LAUNCH(VEC)                                                                                                               \
+    hipLaunchKernelGGL((decoder_inputs_kernel<TT, VEC>), grid, dim3(64 * GLUE_ROWS), 0, st, (const TT*)enc_delta, props_sel, refpoint, \
+                       valid_ratios, L, (const TT*)query_feat, dim_t, (TT*)enc_boxes_out, ref_out, (TT*)sine_out, (TT*)xdec_out, rows, \
+                       nq, d)
+    LWDETR_DISPATCH_T(dtype, { if (vec) GLUE_LAUNCH(true); else GLUE_LAUNCH(false); });
+#undef GLUE_LAUNCH
     return lwdetr_check_launch();
 }
 
