@@ -303,6 +303,15 @@ const char* lwdetr_vit_path_name(int i);
  * msda_backward_{f32,f64}. */
 int lwdetr_msda_path_counts(long* out, int n);
 const char* lwdetr_msda_path_name(int i);
+
+/* The same record for attention.hip: one counter per kernel instantiation that lwdetr_attention can launch, named by rule -
+ * attn_wave_{f32,f16,bf16}_hd{16,32,64}_qt{2,4} and ..._qt2_short (attn_kernel: 32 / 64 queries per wave, the <= 128-key form of the 16-bit types;
+ * no qt4 at hd 64, no short form in f32), attn_win_{f16,bf16}_hd{16,32} (one wave per (sequence, head)), attn_ring_{f16,bf16}_hd{HD}_q{QT}w{NW}u{U}
+ * (the LDS-ring kernel: one name per tuning variant of lwdetr_attention_tuning_cfg, 1000 (U - 1) + 100 QT + NW; the variants whose ring does not fit
+ * the LDS budget - U = 2 at hd 64, U = 4 - answer LWDETR_ERR_UNSUPPORTED and their counters never move), attn_wtile_{f16,bf16} in
+ * LWDETR_EXPERIMENTS builds only. */
+int lwdetr_attn_path_counts(long* out, int n);
+const char* lwdetr_attn_path_name(int i);
 long lwdetr_vit_block_stream_bytes(int C, int has_qkv);
 long lwdetr_vit_block_vec_floats(int C);
 int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, const void* wstream, const float* vec, void* out2,

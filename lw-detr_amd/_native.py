@@ -104,6 +104,9 @@ def lib():
         l.lwdetr_msda_path_counts.argtypes = [C.POINTER(C.c_long), i]
         l.lwdetr_msda_path_name.argtypes = [i]
         l.lwdetr_msda_path_name.restype = C.c_char_p
+        l.lwdetr_attn_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_attn_path_name.argtypes = [i]
+        l.lwdetr_attn_path_name.restype = C.c_char_p
         l.lwdetr_attention_tuning.argtypes = [i]
         l.lwdetr_attention_tuning.restype = None
         l.lwdetr_attention_tuning_cfg.argtypes = [i]
@@ -222,6 +225,15 @@ def msda_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_msda_path_counts(buf, n)
     return {l.lwdetr_msda_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def attn_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_attention in this process (lwdetr_attn_path_counts)."""
+    l = lib()
+    n = l.lwdetr_attn_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_attn_path_counts(buf, n)
+    return {l.lwdetr_attn_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def tuning_set(name: str, value=None):

@@ -17,9 +17,40 @@
 // V^T operand by loading two 8-byte runs per lane. Waves are independent (no LDS, no barriers): K / V^T tiles are
 // re-read through L1/L2, which holds a whole (image, head) slice (1600 x 16 x 2 B x 2 = 100 KB at 640x640).
 #include "common.h"
+#include <atomic>
+#include <cstdio>
 #include <cstdlib>
+#include <type_traits>
+
+// Launch-form record (lwdetr_attn_path_counts; modelled on lwdetr_msda_path_counts): this file is compiled into two objects (Makefile: attention.o and
+// attention_hd16.o), so the counters live in the main object only and every launcher - the hd 16 ring launchers of the second object included - bumps
+// them through this function, which the main object defines. `slot` is one of the ap_*() numbers below.
+extern "C" __attribute__((visibility("hidden"))) void lwdetr_attn_path_bump(int slot);
 
 namespace {
+
+// ---- slots of the launch-form record: one per kernel instantiation the launchers below can name. Slots of instantiations that do not exist (f32 has no
+// short form, hd 64 no 64-query form) get no name and no counter (AttnPathTable). Ring forms: every case of the switch in launch_lds_cfg, in its order.
+constexpr int AP_WAVE = 0, AP_WIN = 27, AP_RING = 31, AP_NCFG = 16, AP_WTILE = AP_RING + 6 * AP_NCFG, AP_SLOTS = AP_WTILE + 2;
+constexpr int kAttnRingCfg[AP_NCFG] = {102, 103, 104, 105, 106, 108, 110, 204, 205, 208, 1104, 1105, 1108, 1110, 3108, 1208};   // 1000 (U - 1) + 100 QT + NW
+template <typename T> constexpr int ap_dtype() { return std::is_same<T, float>::value ? 0 : (std::is_same<T, f16>::value ? 1 : 2); }   // f32, f16, bf16
+constexpr int ap_hd(int hd) { return hd == 16 ? 0 : (hd == 32 ? 1 : 2); }
+template <typename T, int HD, int QT, bool SHORT> constexpr int ap_wave() { return AP_WAVE + ap_dtype<T>() * 9 + ap_hd(HD) * 3 + (SHORT ? 2 : (QT == 4 ? 1 : 0)); }
+template <typename T, int HD> constexpr int ap_win() { return AP_WIN + (ap_dtype<T>() - 1) * 2 + ap_hd(HD); }
+constexpr int ap_cfg(int qt, int nw, int u) {
+    for (int i = 0; i < AP_NCFG; ++i)
+        if (kAttnRingCfg[i] == 1000 * (u - 1) + 100 * qt + nw) return i;
+    return -1;
+}
+template <typename T, int HD, int QT, int NW, int U> constexpr int ap_ring() {
+    static_assert(ap_cfg(QT, NW, U) >= 0, "a ring form without a slot in the launch-form record");
+    return AP_RING + ((ap_dtype<T>() - 1) * 3 + ap_hd(HD)) * AP_NCFG + ap_cfg(QT, NW, U);
+}
+template <typename T> constexpr int ap_wtile() { return AP_WTILE + ap_dtype<T>() - 1; }
+inline int attn_path_done(int slot, int rc) {          // counted only when the launch check succeeded
+    if (rc == LWDETR_OK) lwdetr_attn_path_bump(slot);
+    return rc;
+}
 
 // cross-row reductions on the VALU (v_permlane16_swap / v_permlane32_swap) instead of ds_bpermute through the LDS
 __device__ __forceinline__ float xor16_max(float v) {
@@ -644,7 +675,7 @@ int launch_lds(const lwdetr_attn_desc& p, hipStream_t st) {
     const double bytes = 4.0 * nseq * p.heads * p.keys_per_seq * HD * sizeof(T);
     ProfScope ps(p.kind == 0 ? KID_ATTN_WINDOW : (p.kind == 1 ? KID_ATTN_GLOBAL : KID_ATTN_DECODER), flops, bytes, st);
     hipLaunchKernelGGL((attn_lds_kernel<T, HD, QT, NW, U>), dim3((unsigned)nwg), dim3(NW * 64), 0, st, p);
-    return lwdetr_check_launch();
+    return attn_path_done(ap_ring<T, HD, QT, NW, U>(), lwdetr_check_launch());
     }
 }
 
@@ -920,7 +951,7 @@ int launch_win(const lwdetr_attn_desc& p, hipStream_t st) {
     const int kid = p.kind == 0 ? KID_ATTN_WINDOW : (p.kind == 1 ? KID_ATTN_GLOBAL : KID_ATTN_DECODER);
     ProfScope ps(kid, flops, bytes, st);
     hipLaunchKernelGGL((attn_win_kernel<T, HD>), dim3((unsigned)((npairs + 3) / 4)), dim3(256), 0, st, p);
-    return lwdetr_check_launch();
+    return attn_path_done(ap_win<T, HD>(), lwdetr_check_launch());
 }
 
 // =====================================================================================================================
@@ -1087,7 +1118,7 @@ int launch_wtile(const lwdetr_attn_desc& p, hipStream_t st) {
     const int kid = p.kind == 0 ? KID_ATTN_WINDOW : (p.kind == 1 ? KID_ATTN_GLOBAL : KID_ATTN_DECODER);
     ProfScope ps(kid, flops, bytes, st);
     hipLaunchKernelGGL((attn_wtile_kernel<T>), dim3((unsigned)(p.B * p.seqs_per_img)), dim3(256), lds, st, p);
-    return lwdetr_check_launch();
+    return attn_path_done(ap_wtile<T>(), lwdetr_check_launch());
 }
 #endif
 
@@ -1104,11 +1135,11 @@ int launch_qt(const lwdetr_attn_desc& p, hipStream_t st) {
     if constexpr (QT == 2 && sizeof(T) == 2) {
         if (p.keys_per_seq <= 128 && !short_off) {
             hipLaunchKernelGGL((attn_kernel<T, HD, QT, true>), grid, dim3(256), 0, st, p);
-            return lwdetr_check_launch();
+            return attn_path_done(ap_wave<T, HD, QT, true>(), lwdetr_check_launch());
         }
     }
     hipLaunchKernelGGL((attn_kernel<T, HD, QT>), grid, dim3(256), 0, st, p);
-    return lwdetr_check_launch();
+    return attn_path_done(ap_wave<T, HD, QT, false>(), lwdetr_check_launch());
 }
 
 template <typename T, int HD>
@@ -1176,6 +1207,56 @@ extern "C" __attribute__((visibility("hidden"))) int lwdetr_attn_lds_hd16_impl(c
     return dtype == DT_F16 ? launch_lds_cfg<f16, 16>(*p, (hipStream_t)hip_stream) : launch_lds_cfg<bf16, 16>(*p, (hipStream_t)hip_stream);
 }
 #else
+namespace {
+// names by rule, built once: attn_wave_{f32,f16,bf16}_hd{16,32,64}_qt{2,4} / _qt2_short, attn_win_{f16,bf16}_hd{16,32},
+// attn_ring_{f16,bf16}_hd{HD}_q{QT}w{NW}u{U} (every case of launch_lds_cfg's switch; the forms launch_lds refuses at compile time - U = 2 at hd 64,
+// U = 4 - keep a counter that never moves), attn_wtile_{f16,bf16} in LWDETR_EXPERIMENTS builds
+struct AttnPathTable {
+    int n = 0;
+    int index[AP_SLOTS];
+    char names[AP_SLOTS][40];
+    void add(int slot, const char* fmt, const char* dt, int a = 0, int b = 0, int c = 0, int d = 0) {
+        index[slot] = n;
+        snprintf(names[n++], sizeof(names[0]), fmt, dt, a, b, c, d);
+    }
+    AttnPathTable() {
+        static const char* const dts[3] = {"f32", "f16", "bf16"};
+        static const int hds[3] = {16, 32, 64};
+        for (int i = 0; i < AP_SLOTS; ++i) index[i] = -1;
+        for (int dt = 0; dt < 3; ++dt)
+            for (int h = 0; h < 3; ++h) {
+                add(AP_WAVE + dt * 9 + h * 3, "attn_wave_%s_hd%d_qt2", dts[dt], hds[h]);
+                if (h < 2) add(AP_WAVE + dt * 9 + h * 3 + 1, "attn_wave_%s_hd%d_qt4", dts[dt], hds[h]);       // launch(): hd 64 keeps 32 queries per wave
+                if (dt > 0) add(AP_WAVE + dt * 9 + h * 3 + 2, "attn_wave_%s_hd%d_qt2_short", dts[dt], hds[h]);   // launch_qt(): 16-bit types only
+            }
+        for (int dt = 1; dt < 3; ++dt)
+            for (int h = 0; h < 2; ++h) add(AP_WIN + (dt - 1) * 2 + h, "attn_win_%s_hd%d", dts[dt], hds[h]);
+        for (int dt = 1; dt < 3; ++dt)
+            for (int h = 0; h < 3; ++h)
+                for (int c = 0; c < AP_NCFG; ++c) {
+                    const int cfg = kAttnRingCfg[c];
+                    add(AP_RING + ((dt - 1) * 3 + h) * AP_NCFG + c, "attn_ring_%s_hd%d_q%dw%du%d", dts[dt], hds[h], cfg % 1000 / 100, cfg % 100, cfg / 1000 + 1);
+                }
+#ifdef LWDETR_EXPERIMENTS
+        for (int dt = 1; dt < 3; ++dt) add(AP_WTILE + dt - 1, "attn_wtile_%s", dts[dt]);
+#endif
+    }
+};
+const AttnPathTable& attn_paths() { static const AttnPathTable t; return t; }
+std::atomic<long> g_attn_path[AP_SLOTS];
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) void lwdetr_attn_path_bump(int slot) {
+    const int i = slot >= 0 && slot < AP_SLOTS ? attn_paths().index[slot] : -1;
+    if (i >= 0) g_attn_path[i].fetch_add(1, std::memory_order_relaxed);
+}
+extern "C" int lwdetr_attn_path_counts(long* out, int n) {
+    const int count = attn_paths().n;
+    for (int i = 0; out && i < n && i < count; ++i) out[i] = g_attn_path[i].load(std::memory_order_relaxed);
+    return count;
+}
+extern "C" const char* lwdetr_attn_path_name(int i) { return i >= 0 && i < attn_paths().n ? attn_paths().names[i] : nullptr; }
+
 extern "C" void lwdetr_attention_tuning(int lds_mode) { g_attn_lds_mode = lds_mode; }
 extern "C" void lwdetr_attention_tuning_cfg(int cfg) { g_attn_lds_cfg = cfg; }
 

@@ -220,3 +220,22 @@ def msda_served_by(form, launches=1):
         assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
     else:
         assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"
+
+
+@contextlib.contextmanager
+def attn_served_by(form, launches=1):
+    """As served_by for the record of attention.hip (lwdetr_attn_path_counts): the lwdetr_attention launches inside the block went to exactly the
+    instantiation `form` (a name of lwdetr_attn_path_name: "attn_wave_f16_hd16_qt2_short", "attn_win_bf16_hd32", "attn_ring_f16_hd64_q2w8u1", ...),
+    `launches` times (None: at least once), and to no other."""
+    import torch
+    from lwdetr_amd import _native
+    before = _native.attn_path_counts()
+    assert form in before, f"unknown attention kernel form {form!r}: {sorted(before)}"
+    yield
+    torch.cuda.synchronize()
+    after = _native.attn_path_counts()
+    delta = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+    if launches is None:
+        assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
+    else:
+        assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"

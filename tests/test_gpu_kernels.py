@@ -1,11 +1,12 @@
 """GPU: every HIP kernel of liblwdetr_hip.so against a plain PyTorch fp32 reference of the same op."""
+import contextlib
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import served_by
+from helpers import attn_served_by, served_by
 
 pytestmark = pytest.mark.gpu
 
@@ -345,10 +346,14 @@ def _attention_case(dtype, hd, geom, cfg):
     use_lds = slack or geom in ("global1600", "holes3648", "global704")
     _native.lib().lwdetr_attention_tuning(3 if use_lds else -1)
     _native.lib().lwdetr_attention_tuning_cfg(cfg)
+    # a tuning variant names its instantiation: the launch-form record (lwdetr_attn_path_counts) must show exactly that one
+    pinned = contextlib.nullcontext() if not cfg else attn_served_by(
+        "attn_ring_%s_hd%d_q%dw%du%d" % (str(dtype).split(".")[-1].replace("float", "f"), hd, cfg % 1000 // 100, cfg % 100, cfg // 1000 + 1))
     try:
-        K.AttnOp(qs, k, vt, out, B=b, heads=heads, hd=hd, Tp=tp, ldo=heads * hd,
-                 seqs_per_img=spi, seq_tok_stride=twp if spi == 16 else tp, keys_per_seq=keys, sub_stride=twp,
-                 sub_len=tw, kind=0, vt_slack=slack)()
+        with pinned:
+            K.AttnOp(qs, k, vt, out, B=b, heads=heads, hd=hd, Tp=tp, ldo=heads * hd,
+                     seqs_per_img=spi, seq_tok_stride=twp if spi == 16 else tp, keys_per_seq=keys, sub_stride=twp,
+                     sub_len=tw, kind=0, vt_slack=slack)()
     finally:
         _native.lib().lwdetr_attention_tuning(-1)
         _native.lib().lwdetr_attention_tuning_cfg(0)
