@@ -28,6 +28,8 @@
  *   lwdetr_ffn_partial/_finish models/transformer.py:507-512, :397-400 (decoder FFN + norm3 + decoder.norm)
  *   lwdetr_layernorm           nn.LayerNorm call sites (vit.py:199,:217; transformer.py:231,:499,:511,:516,:398) and
  *                              the channel LayerNorm of models/backbone/projector.py:21-47
+ *   lwdetr_match_cost/_assign  models/matcher.py:50-111 (HungarianMatcher.forward: cost matrix, scipy linear_sum_assignment)
+ *   lwdetr_criterion_partials/_finish  models/lwdetr.py:256-380, :458-483 (SetCriterion's losses, evaluation only)
  */
 #ifndef LWDETR_HIP_H
 #define LWDETR_HIP_H
@@ -441,6 +443,49 @@ int lwdetr_postprocess(const void* logits, const void* boxes, const float* targe
  * (replaces the pickled per-image dicts of util/misc.py:99-139; labels < 2^24 are exact in f32). */
 int lwdetr_postprocess_packed(const void* logits, const void* boxes, const float* target_sizes, int B, int nq, int ncls, int K,
                               float* packed, int dtype, void* hip_stream);
+
+/* ---- evaluation criterion: Hungarian matcher and losses, inference only (models/matcher.py:50-111, models/lwdetr.py:256-455) ----
+ * One call serves every "layer" of a criterion call (final, aux 0..n, enc; at most LWDETR_CRIT_MAX_LAYERS) through a HOST array of
+ * descriptors: logits (B,nq,C) and boxes (B,nq,4 cxcywh) contiguous in `dtype`, converted to f32 on load. Targets arrive packed:
+ * labels (sumT) int64 in [0, C) (out-of-range labels are clamped for the load), tboxes (sumT,4) f32 cxcywh, offsets (B+1) int32 on the
+ * DEVICE = prefix sums of the per-image target counts; counts (B) int32 on the HOST are the same counts, from which the entries size
+ * their launches (a kernel that finds offsets and counts in disagreement writes nothing for that image and sets status 2).
+ * lwdetr_match_cost     : cost[layer][off_b + t][q] = w_bbox L1 + w_class (pos - neg) + w_giou (-GIoU) in f32, in the reference's operation
+ *                         order (matcher.py:71-94, util/box_ops.py:21-25, :36-73), only an image's own targets; cost (layers, sumT, nq) f32.
+ * lwdetr_match_assign   : rectangular linear assignment per (layer, image): shortest augmenting paths with f64 duals (the algorithm and the
+ *                         optimum of scipy.optimize.linear_sum_assignment), one wave per problem. nq <= LWDETR_MATCH_MAX_NQ, T_b <= nq
+ *                         (else LWDETR_ERR_UNSUPPORTED). Every loop's trip count is fixed by T_b and nq, so non-finite costs terminate
+ *                         too. idx_q / idx_t (layers, sumT) int64: the T_b pairs of image b at [layer][off_b ...], ascending in the query
+ *                         index (scipy's row order), idx_t local to the image. status (layers, B) int32: non-zero when the problem saw a
+ *                         non-finite cost (1) or inconsistent offsets (2). steps (layers, B) int32 or NULL: shortest-path steps taken.
+ * lwdetr_match_assign_host : the same solver instantiated for the host (the lanes of the wave emulated) on a HOST cost matrix (T, nq).
+ * lwdetr_criterion_partials: per (layer, image, chunk of LWDETR_CRIT_QCHUNK queries) the f32 sums {loss_ce terms, |box - target|,
+ *                         1 - GIoU, rows whose arg-max is not the last class, matched rows whose arg-max is the label}; the matched
+ *                         (b, q) -> target map is rebuilt per chunk from the assignment. loss_form 0 = sigmoid focal loss
+ *                         (lwdetr.py:330-339, :458-483), 1 = IA-BCE (lwdetr.py:266-290). partials: lwdetr_criterion_partials_floats() f32.
+ * lwdetr_criterion_finish: adds the partials in a fixed order in f64 and writes out (layers, 5) f32 = loss_ce, class_error (layers with
+ *                         descriptor.class_error != 0, else 0), loss_bbox, loss_giou, cardinality_error. No floating-point atomics. */
+#define LWDETR_CRIT_MAX_LAYERS 8
+#define LWDETR_MATCH_MAX_NQ 1024
+#define LWDETR_CRIT_QCHUNK 32
+typedef struct {
+    const void* logits;
+    const void* boxes;
+    int class_error;
+    int reserved;
+} lwdetr_crit_layer;
+int lwdetr_match_cost(const lwdetr_crit_layer* layers, int nlayers, int B, int nq, int C, const int64_t* labels, const float* tboxes,
+                      const int32_t* offsets, const int32_t* counts, float w_class, float w_bbox, float w_giou, float alpha, float* cost,
+                      int dtype, void* hip_stream);
+int lwdetr_match_assign(const float* cost, const int32_t* offsets, const int32_t* counts, int nlayers, int B, int nq, int64_t* idx_q,
+                        int64_t* idx_t, int32_t* status, int32_t* steps, void* hip_stream);
+int lwdetr_match_assign_host(const float* cost, int nq, int T, int64_t* idx_q, int64_t* idx_t, int32_t* status, int32_t* steps);
+long lwdetr_criterion_partials_floats(int nlayers, int B, int nq);
+int lwdetr_criterion_partials(const lwdetr_crit_layer* layers, int nlayers, int B, int nq, int C, const int64_t* labels,
+                              const float* tboxes, const int32_t* offsets, const int32_t* counts, const int64_t* idx_q,
+                              const int64_t* idx_t, int loss_form, float alpha, float* partials, int dtype, void* hip_stream);
+int lwdetr_criterion_finish(const float* partials, const lwdetr_crit_layer* layers, const int32_t* offsets, const int32_t* counts,
+                            int nlayers, int B, int nq, int loss_form, float num_boxes, float* out, void* hip_stream);
 
 /* ---- input side: uint8 HWC -> Pillow-exact bilinear square resize -> ToTensor -> Normalize -> NCHW --
  * Replaces datasets/transforms.py:223-231 (SquareResize = PIL.Image.resize((S,S), BILINEAR)), :437-443 (Normalize) and

@@ -12,3 +12,11 @@ __version__ = "0.1.0"
 def build_model(args):
     from .models import build_model as _build
     return _build(args)
+
+
+def __getattr__(name):
+    # the criterion classes of lwdetr_amd.models, resolved lazily as build_model resolves the model
+    if name in ("HungarianMatcher", "SetCriterion", "build_criterion", "build_matcher"):
+        from . import models
+        return getattr(models, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

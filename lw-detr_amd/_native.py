@@ -68,6 +68,14 @@ class ChainDesc(C.Structure):
                 ("D", C.c_int), ("nst", C.c_int), ("st", ChainStage * 6)]
 
 
+CRIT_MAX_LAYERS, MATCH_MAX_NQ, CRIT_QCHUNK = 8, 1024, 32
+LOSS_FOCAL, LOSS_IA_BCE = 0, 1
+
+
+class CritLayer(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("boxes", C.c_void_p), ("class_error", C.c_int), ("reserved", C.c_int)]
+
+
 def is_built() -> bool:
     return os.path.exists(LIB_PATH)
 
@@ -162,6 +170,14 @@ def lib():
         l.lwdetr_postprocess_packed.argtypes = [vp, vp, vp, i, i, i, i, vp, i, vp]
         l.lwdetr_finalize_outputs.argtypes = [vp, vp, lg, vp, lg, vp, lg, i, vp, lg, i, vp]
         l.lwdetr_resize_normalize.argtypes = [vp, i, i, vp, vp, vp, vp, i, i, vp]
+        pl = C.POINTER(CritLayer)
+        l.lwdetr_match_cost.argtypes = [pl, i, i, i, i, vp, vp, vp, vp, f, f, f, f, vp, i, vp]
+        l.lwdetr_match_assign.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
+        l.lwdetr_match_assign_host.argtypes = [vp, i, i, vp, vp, vp, vp]
+        l.lwdetr_criterion_partials_floats.argtypes = [i, i, i]
+        l.lwdetr_criterion_partials_floats.restype = C.c_long
+        l.lwdetr_criterion_partials.argtypes = [pl, i, i, i, i, vp, vp, vp, vp, vp, vp, i, f, vp, i, vp]
+        l.lwdetr_criterion_finish.argtypes = [vp, pl, vp, vp, i, i, i, i, f, vp, vp]
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -170,7 +186,8 @@ def lib():
         l.lwdetr_prof_collect.argtypes = [vp, vp, vp, vp, i]
         for fn in ("lwdetr_msda_forward", "lwdetr_msda_backward", "lwdetr_msda_fused_forward", "lwdetr_gemm", "lwdetr_attention",
                    "lwdetr_layernorm", "lwdetr_layernorm_chain", "lwdetr_row_stats", "lwdetr_enc_chain", "lwdetr_enc_chain_check", "lwdetr_row_chain", "lwdetr_mlp_fused", "lwdetr_vit_block_few", "lwdetr_vit_block", "lwdetr_vit_qkv", "lwdetr_vit_stem", "lwdetr_ffn_splits", "lwdetr_ffn_partial", "lwdetr_ffn_finish", "lwdetr_select_gather", "lwdetr_decoder_inputs",
-                   "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
+                   "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_match_cost", "lwdetr_match_assign", "lwdetr_match_assign_host",
+                   "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
             getattr(l, fn).restype = C.c_int
         _lib = l
     return _lib

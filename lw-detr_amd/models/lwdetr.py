@@ -319,9 +319,11 @@ class PostProcess(nn.Module):
 def build(args):
     """``build_model(args) -> (model, criterion, postprocessors)`` (reference ``lwdetr.py:562-619``).
 
-    The training criterion (Hungarian matcher + losses, ``lwdetr.py:218-506``, ``matcher.py``) is outside this
-    package's scope: when the reference's ``models.lwdetr.SetCriterion`` is importable (i.e. this package is dropped
-    into the reference repository) it is built exactly as the reference does; otherwise ``criterion`` is ``None``."""
+    The criterion (Hungarian matcher + losses, ``lwdetr.py:218-506``, ``matcher.py``): when the reference's
+    ``models.lwdetr.SetCriterion`` is importable (i.e. this package is dropped into the reference repository) it is built
+    exactly as the reference does, unless ``args.native_criterion`` is true. Otherwise ``criterion`` is this package's
+    inference-only ``models.criterion.SetCriterion`` (``engine.evaluate`` runs on it), or ``None`` when ``args`` asks for a
+    loss form it does not implement (``use_varifocal_loss``, ``use_position_supervised_loss``)."""
     num_classes = 20 if args.dataset_file != "coco" else 91
     if args.dataset_file == "o365":
         num_classes = 366
@@ -343,7 +345,10 @@ def build(args):
                    aux_loss=args.aux_loss, group_detr=args.group_detr, two_stage=args.two_stage,
                    lite_refpoint_refine=args.lite_refpoint_refine, bbox_reparam=args.bbox_reparam, args=args)
     model.eval()
-    criterion = _reference_criterion(args, num_classes)
+    criterion = None if getattr(args, "native_criterion", False) else _reference_criterion(args, num_classes)
+    if criterion is None:
+        from .criterion import build_criterion, native_criterion_supported
+        criterion = build_criterion(args, num_classes) if native_criterion_supported(args) else None
     postprocessors = {"bbox": PostProcess(num_select=args.num_select)}
     return model, criterion, postprocessors
 
