@@ -30,6 +30,7 @@
  *                              the channel LayerNorm of models/backbone/projector.py:21-47
  *   lwdetr_match_cost/_assign  models/matcher.py:50-111 (HungarianMatcher.forward: cost matrix, scipy linear_sum_assignment)
  *   lwdetr_criterion_partials/_finish  models/lwdetr.py:256-380, :458-483 (SetCriterion's losses, evaluation only)
+ *   lwdetr_cocoeval_match/_npig/_curves  datasets/coco_eval.py:26-78, :219-264 (pycocotools COCOeval for boxes: evaluateImg, accumulate)
  */
 #ifndef LWDETR_HIP_H
 #define LWDETR_HIP_H
@@ -486,6 +487,71 @@ int lwdetr_criterion_partials(const lwdetr_crit_layer* layers, int nlayers, int 
                               const int64_t* idx_t, int loss_form, float alpha, float* partials, int dtype, void* hip_stream);
 int lwdetr_criterion_finish(const float* partials, const lwdetr_crit_layer* layers, const int32_t* offsets, const int32_t* counts,
                             int nlayers, int B, int nq, int loss_form, float num_boxes, float* out, void* hip_stream);
+
+/* ---- COCO box evaluator: pycocotools' COCOeval for iouType 'bbox' (the class behind datasets/coco_eval.py:26-78, :219-264; the reference's
+ * engine.py:104-105, :145-163 drives it). All geometry and curve arithmetic is f64 in COCOeval's operation order, FP contraction off.
+ * The ground truth is packed once (lwdetr_coco_gt, a HOST struct of DEVICE pointers; HOST pointers for the _host form): image rows in
+ * ascending image id, categories dense in ascending category id, the annotations of an image grouped by dense category with the dataset
+ * order kept inside a group (COCO.getAnnIds / COCOeval._prepare). grp_off (n_images * n_cats + 1) int32 are the prefix offsets of the
+ * (row, category) groups - grp_off[row * n_cats] is the image's own offset; box (n_ann, 4) f64 xywh; area (n_ann) f64 = the annotation's
+ * `area` key; crowd (n_ann) uint8 = iscrowd; cat (n_ann) int32 dense category; cat_lut (lut_size) int32: category id -> dense index or -1.
+ * max_group = the largest group, as the host counted it.
+ * lwdetr_cocoeval_match : COCOeval.computeIoU + evaluateImg for one batch: dets (B, K, 6) f32 records (score, label, x0, y0, x1, y1),
+ *     rows (B) int32 = the images' rows in the table (a row outside [0, n_images) keeps nothing). What it reproduces, trap by trap:
+ *     - detection box -> xywh with w = x1 - x0, h = y1 - y0 IN f32 (convert_to_xywh runs on the f32 tensor, coco_eval.py:176-178), then
+ *       everything f64; detection area = w * h in f64 (COCO.loadRes). Labels are category ids; an id outside the category list is dropped.
+ *     - per (image, category): descending score, stable in the detection index (argsort(-score, kind='mergesort')), first 100 = maxDets[-1].
+ *     - IoU as maskApi.c bbIou: w = min(dx+dw, gx+gw) - max(dx, gx), w <= 0 -> 0, same for h; i = w*h; u = da for a crowd gt, else
+ *       da + ga - i with ga = gw*gh; i / u.
+ *     - a gt is ignored when iscrowd is set or `area` is outside [lo, hi], BOTH ends inclusive (area 1024 is small and medium); the
+ *       annotation's `ignore` key has no effect (_prepare overwrites it with iscrowd). gts are walked non-ignored first, stable.
+ *     - greedy rule per threshold t, detections in score order: iou = min(t, 1 - 1e-10), m = -1; walk the gts; skip one already matched at
+ *       t unless it is a crowd; stop at the first ignored gt once m is a non-ignored gt; skip when ious[d, g] < iou (STRICTLY less: an equal
+ *       IoU moves the match to the later gt); else iou = ious[d, g], m = g. A matched detection inherits the gt's ignore flag; an unmatched
+ *       one is ignored when its own area is outside the range.
+ *     - iou_thrs (10) f64 on the HOST = np.linspace(.5, .95, 10), passed in, never recomputed. Area ranges are Params.areaRng.
+ *     - "matched" means "has a gt". pycocotools tests the stored gt ID for truth (dtm == 0, cocoeval.py evaluateImg / accumulate), so an
+ *       annotation with id 0 reads as unmatched there; that quirk is NOT reproduced.
+ *     Out, per detection slot b * K + d: out_cat int32 dense category (-1: dropped - unknown label or rank >= 100), out_score f32,
+ *     out_rank int32 rank inside its (image, category) list (-1: dropped), out_matched / out_ignored int64: bit (area * 10 + threshold).
+ * lwdetr_cocoeval_match_host : the same per-(image, category) code instantiated for the host on HOST arrays, the lanes emulated.
+ * lwdetr_cocoeval_npig : npig (n_cats, 4) int32 = non-ignored gts per (category, area range) over rows (n_rows) int32, the EVALUATED images,
+ *     each listed once (accumulate's npig = count_nonzero(gtIg == 0)); zeroes npig first. Integer atomics.
+ * lwdetr_cocoeval_curves : COCOeval.accumulate over the store ordered by (category, descending score, image id, in-image order) - the
+ *     mergesort of accumulate over per-image lists concatenated in sorted image id order. seg_off (n_cats + 1) int64: the categories'
+ *     segments. Per (category, area, maxDet in {1, 10, 100}, threshold), a detection taking part iff rank < maxDet: integer running tp / fp,
+ *     rc = tp / npig, pr = tp / (fp + tp + 2.220446049250313e-16), the right-to-left running maximum of pr, and per recall threshold
+ *     (rec_thrs (101) f64 on the HOST, ascending = np.linspace(0, 1, 101)) the first index with rc >= thr (searchsorted side 'left'):
+ *     precision and score from that index, 0 when there is none; recall = rc[-1], 0 without detections. Groups with npig == 0 are not
+ *     written: the caller pre-fills with -1. precision / scores (10, 101, n_cats, 4, 3) f64, recall (10, n_cats, 4, 3) f64.
+ * Limits, LWDETR_ERR_UNSUPPORTED before any launch, never truncated: K <= LWDETR_COCOEVAL_MAX_DETS detections per image, max_group <=
+ * LWDETR_COCOEVAL_MAX_GROUP annotations per (image, category), n_cats <= LWDETR_COCOEVAL_MAX_CATS. No entry synchronises with the host;
+ * no floating-point atomics. */
+#define LWDETR_COCOEVAL_MAX_DETS 1024
+#define LWDETR_COCOEVAL_MAX_GROUP 256
+#define LWDETR_COCOEVAL_MAX_CATS 1024
+#define LWDETR_COCOEVAL_KEEP 100
+#define LWDETR_COCOEVAL_NTHR 10
+#define LWDETR_COCOEVAL_NAREA 4
+#define LWDETR_COCOEVAL_NREC 101
+typedef struct {
+    const int32_t* grp_off;
+    const double* box;
+    const double* area;
+    const uint8_t* crowd;
+    const int32_t* cat;
+    const int32_t* cat_lut;
+    int n_images, n_cats, lut_size, n_ann, max_group, reserved;
+} lwdetr_coco_gt;
+int lwdetr_cocoeval_match(const lwdetr_coco_gt* gt, const float* dets, const int32_t* rows, int B, int K, const double* iou_thrs,
+                          int32_t* out_cat, float* out_score, int32_t* out_rank, int64_t* out_matched, int64_t* out_ignored,
+                          void* hip_stream);
+int lwdetr_cocoeval_match_host(const lwdetr_coco_gt* gt, const float* dets, const int32_t* rows, int B, int K, const double* iou_thrs,
+                               int32_t* out_cat, float* out_score, int32_t* out_rank, int64_t* out_matched, int64_t* out_ignored);
+int lwdetr_cocoeval_npig(const lwdetr_coco_gt* gt, const int32_t* rows, int n_rows, int32_t* npig, void* hip_stream);
+int lwdetr_cocoeval_curves(const int64_t* seg_off, const float* score, const int32_t* rank, const int64_t* matched, const int64_t* ignored,
+                           const int32_t* npig, const double* rec_thrs, int n_cats, long n_store, double* precision, double* scores,
+                           double* recall, void* hip_stream);
 
 /* ---- input side: uint8 HWC -> Pillow-exact bilinear square resize -> ToTensor -> Normalize -> NCHW --
  * Replaces datasets/transforms.py:223-231 (SquareResize = PIL.Image.resize((S,S), BILINEAR)), :437-443 (Normalize) and

@@ -19,4 +19,7 @@ def __getattr__(name):
     if name in ("HungarianMatcher", "SetCriterion", "build_criterion", "build_matcher"):
         from . import models
         return getattr(models, name)
+    if name in ("CocoEvaluator", "CocoGroundTruth"):       # the native COCO box evaluator (coco_eval.py), resolved lazily as well
+        from . import coco_eval
+        return getattr(coco_eval, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

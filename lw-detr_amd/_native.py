@@ -76,6 +76,15 @@ class CritLayer(C.Structure):
     _fields_ = [("logits", C.c_void_p), ("boxes", C.c_void_p), ("class_error", C.c_int), ("reserved", C.c_int)]
 
 
+COCOEVAL_MAX_DETS, COCOEVAL_MAX_GROUP, COCOEVAL_MAX_CATS, COCOEVAL_KEEP = 1024, 256, 1024, 100
+
+
+class CocoGt(C.Structure):
+    _fields_ = [("grp_off", C.c_void_p), ("box", C.c_void_p), ("area", C.c_void_p), ("crowd", C.c_void_p), ("cat", C.c_void_p),
+                ("cat_lut", C.c_void_p), ("n_images", C.c_int), ("n_cats", C.c_int), ("lut_size", C.c_int), ("n_ann", C.c_int),
+                ("max_group", C.c_int), ("reserved", C.c_int)]
+
+
 def is_built() -> bool:
     return os.path.exists(LIB_PATH)
 
@@ -178,6 +187,11 @@ def lib():
         l.lwdetr_criterion_partials_floats.restype = C.c_long
         l.lwdetr_criterion_partials.argtypes = [pl, i, i, i, i, vp, vp, vp, vp, vp, vp, i, f, vp, i, vp]
         l.lwdetr_criterion_finish.argtypes = [vp, pl, vp, vp, i, i, i, i, f, vp, vp]
+        pg = C.POINTER(CocoGt)
+        l.lwdetr_cocoeval_match.argtypes = [pg, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp]
+        l.lwdetr_cocoeval_match_host.argtypes = [pg, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
+        l.lwdetr_cocoeval_npig.argtypes = [pg, vp, i, vp, vp]
+        l.lwdetr_cocoeval_curves.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, lg, vp, vp, vp, vp]
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -187,7 +201,8 @@ def lib():
         for fn in ("lwdetr_msda_forward", "lwdetr_msda_backward", "lwdetr_msda_fused_forward", "lwdetr_gemm", "lwdetr_attention",
                    "lwdetr_layernorm", "lwdetr_layernorm_chain", "lwdetr_row_stats", "lwdetr_enc_chain", "lwdetr_enc_chain_check", "lwdetr_row_chain", "lwdetr_mlp_fused", "lwdetr_vit_block_few", "lwdetr_vit_block", "lwdetr_vit_qkv", "lwdetr_vit_stem", "lwdetr_ffn_splits", "lwdetr_ffn_partial", "lwdetr_ffn_finish", "lwdetr_select_gather", "lwdetr_decoder_inputs",
                    "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_match_cost", "lwdetr_match_assign", "lwdetr_match_assign_host",
-                   "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
+                   "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_cocoeval_match", "lwdetr_cocoeval_match_host", "lwdetr_cocoeval_npig",
+                   "lwdetr_cocoeval_curves", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
             getattr(l, fn).restype = C.c_int
         _lib = l
     return _lib

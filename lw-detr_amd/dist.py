@@ -164,6 +164,7 @@ def detect_sharded(detect_fn, images, target_sizes):
 # The reference updates a CocoEvaluator on every rank and merges the per-rank pycocotools state through pickled
 # all_gathers (datasets/coco_eval.py:56-69, :181-200, engine.py:142-157); with the detections already gathered as one
 # fixed-shape tensor, rank 0 can run the stock evaluator on the full result set and no evaluator state crosses ranks.
+# (lwdetr_amd.CocoEvaluator, coco_eval.py, is the other way: every rank scores its shard on its GPU and the per-detection records are gathered.)
 _ID_BITS = 21                                    # image ids travel as three 21-bit limbs: exact in f32, ids < 2^63
 
 
