@@ -488,6 +488,48 @@ int lwdetr_criterion_partials(const lwdetr_crit_layer* layers, int nlayers, int 
 int lwdetr_criterion_finish(const float* partials, const lwdetr_crit_layer* layers, const int32_t* offsets, const int32_t* counts,
                             int nlayers, int B, int nq, int loss_form, float num_boxes, float* out, void* hip_stream);
 
+/* ---- training criterion: grouped matching, four loss forms, gradients (models/lwdetr.py:218-506 in train() mode, matcher.py:50-111) ----
+ * The conventions of the evaluation criterion above hold (layer descriptors, packed targets, device offsets beside host counts).
+ * `groups` = group_detr: nq % groups == 0, nq / groups <= LWDETR_MATCH_MAX_NQ and T_b <= nq / groups, checked on the host counts before
+ * any launch (LWDETR_ERR_UNSUPPORTED otherwise). The cost matrix is lwdetr_match_cost's: a pair's cost does not depend on the group.
+ * lwdetr_match_assign_groups : one wave per (layer, image, group) on the column slice [g nq/G, (g+1) nq/G) of the cost; the solver, trip
+ *                         counts and non-finite-cost guarantee of lwdetr_match_assign. idx_q / idx_t (layers, groups, sumT) int64: the T_b
+ *                         pairs of image b and group g at [layer][g][off_b ...], query indices global (offset by g nq/G) and ascending
+ *                         inside the group. status / steps (layers, B, groups) int32 (steps may be NULL).
+ * lwdetr_criterion_train_partials / _finish : as lwdetr_criterion_partials / _finish with groups and loss_form 0 = sigmoid focal loss,
+ *                         1 = IA-BCE, 2 = varifocal (lwdetr.py:313-328, :486-494), 3 = position-supervised (:292-311, :497-506; the
+ *                         per-image normaliser is the image's largest matched IoU over all groups, taken inside the partials launch).
+ *                         partials: lwdetr_criterion_partials_floats() f32. class_error is over the groups * sumT matched rows,
+ *                         cardinality_error counts all nq rows against T_b. With groups = 1 and forms 0 / 1 the values are those of
+ *                         lwdetr_criterion_partials / _finish.
+ * lwdetr_criterion_backward : one launch for all layers. grad_out (layers, 5) f32 on the DEVICE is the gradient with respect to _finish's
+ *                         `out`; `grads` mirrors `layers` (logits = d/d logits (B,nq,C), boxes = d/d boxes (B,nq,4), in `dtype`, written
+ *                         through the const pointers; class_error ignored). Every element of every gradient is written exactly once;
+ *                         box gradients of unmatched queries are zero. 1 / num_boxes and mean(1) * nq are applied in the kernel. The
+ *                         graph differentiated is the reference's: IoU targets and IA-BCE's t are constants, the modulating weights are not.
+ * lwdetr_criterion_grad_host : the same per-element and per-pair derivative functions on HOST arrays for one image: logits (nq, C) and
+ *                         boxes (nq, 4) f32, labels (T), tboxes (T, 4), `npairs` pairs (idx_q, idx_t; idx_t local), grad_out (5) on the
+ *                         host; writes grad_logits (nq, C) and grad_boxes (nq, 4) f32. */
+#define LWDETR_LOSS_FOCAL 0
+#define LWDETR_LOSS_IA_BCE 1
+#define LWDETR_LOSS_VARIFOCAL 2
+#define LWDETR_LOSS_POSITION_SUPERVISED 3
+int lwdetr_match_assign_groups(const float* cost, const int32_t* offsets, const int32_t* counts, int nlayers, int B, int nq, int groups,
+                               int64_t* idx_q, int64_t* idx_t, int32_t* status, int32_t* steps, void* hip_stream);
+int lwdetr_criterion_train_partials(const lwdetr_crit_layer* layers, int nlayers, int B, int nq, int C, const int64_t* labels,
+                                    const float* tboxes, const int32_t* offsets, const int32_t* counts, const int64_t* idx_q,
+                                    const int64_t* idx_t, int groups, int loss_form, float alpha, float* partials, int dtype,
+                                    void* hip_stream);
+int lwdetr_criterion_train_finish(const float* partials, const lwdetr_crit_layer* layers, const int32_t* offsets, const int32_t* counts,
+                                  int nlayers, int B, int nq, int groups, int loss_form, float num_boxes, float* out, void* hip_stream);
+int lwdetr_criterion_backward(const lwdetr_crit_layer* layers, const lwdetr_crit_layer* grads, int nlayers, int B, int nq, int C,
+                              const int64_t* labels, const float* tboxes, const int32_t* offsets, const int32_t* counts,
+                              const int64_t* idx_q, const int64_t* idx_t, int groups, int loss_form, float alpha, float num_boxes,
+                              const float* grad_out, int dtype, void* hip_stream);
+int lwdetr_criterion_grad_host(const float* logits, const float* boxes, int nq, int C, const int64_t* labels, const float* tboxes, int T,
+                               const int64_t* idx_q, const int64_t* idx_t, int npairs, int loss_form, float alpha, float num_boxes,
+                               const float* grad_out, float* grad_logits, float* grad_boxes);
+
 /* ---- COCO box evaluator: pycocotools' COCOeval for iouType 'bbox' (the class behind datasets/coco_eval.py:26-78, :219-264; the reference's
  * engine.py:104-105, :145-163 drives it). All geometry and curve arithmetic is f64 in COCOeval's operation order, FP contraction off.
  * The ground truth is packed once (lwdetr_coco_gt, a HOST struct of DEVICE pointers; HOST pointers for the _host form): image rows in

@@ -16,7 +16,8 @@ def build_model(args):
 
 def __getattr__(name):
     # the criterion classes of lwdetr_amd.models, resolved lazily as build_model resolves the model
-    if name in ("HungarianMatcher", "SetCriterion", "build_criterion", "build_matcher"):
+    if name in ("HungarianMatcher", "SetCriterion", "build_criterion", "build_matcher", "GroupHungarianMatcher", "TrainSetCriterion",
+                "build_group_matcher", "build_train_criterion"):
         from . import models
         return getattr(models, name)
     if name in ("CocoEvaluator", "CocoGroundTruth"):       # the native COCO box evaluator (coco_eval.py), resolved lazily as well

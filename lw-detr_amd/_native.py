@@ -70,6 +70,7 @@ class ChainDesc(C.Structure):
 
 CRIT_MAX_LAYERS, MATCH_MAX_NQ, CRIT_QCHUNK = 8, 1024, 32
 LOSS_FOCAL, LOSS_IA_BCE = 0, 1
+LOSS_VARIFOCAL, LOSS_POSITION_SUPERVISED = 2, 3
 
 
 class CritLayer(C.Structure):
@@ -187,6 +188,11 @@ def lib():
         l.lwdetr_criterion_partials_floats.restype = C.c_long
         l.lwdetr_criterion_partials.argtypes = [pl, i, i, i, i, vp, vp, vp, vp, vp, vp, i, f, vp, i, vp]
         l.lwdetr_criterion_finish.argtypes = [vp, pl, vp, vp, i, i, i, i, f, vp, vp]
+        l.lwdetr_match_assign_groups.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp]
+        l.lwdetr_criterion_train_partials.argtypes = [pl, i, i, i, i, vp, vp, vp, vp, vp, vp, i, i, f, vp, i, vp]
+        l.lwdetr_criterion_train_finish.argtypes = [vp, pl, vp, vp, i, i, i, i, i, f, vp, vp]
+        l.lwdetr_criterion_backward.argtypes = [pl, pl, i, i, i, i, vp, vp, vp, vp, vp, vp, i, i, f, f, vp, i, vp]
+        l.lwdetr_criterion_grad_host.argtypes = [vp, vp, i, i, vp, vp, i, vp, vp, i, i, f, f, vp, vp, vp]
         pg = C.POINTER(CocoGt)
         l.lwdetr_cocoeval_match.argtypes = [pg, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp]
         l.lwdetr_cocoeval_match_host.argtypes = [pg, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
@@ -201,7 +207,8 @@ def lib():
         for fn in ("lwdetr_msda_forward", "lwdetr_msda_backward", "lwdetr_msda_fused_forward", "lwdetr_gemm", "lwdetr_attention",
                    "lwdetr_layernorm", "lwdetr_layernorm_chain", "lwdetr_row_stats", "lwdetr_enc_chain", "lwdetr_enc_chain_check", "lwdetr_row_chain", "lwdetr_mlp_fused", "lwdetr_vit_block_few", "lwdetr_vit_block", "lwdetr_vit_qkv", "lwdetr_vit_stem", "lwdetr_ffn_splits", "lwdetr_ffn_partial", "lwdetr_ffn_finish", "lwdetr_select_gather", "lwdetr_decoder_inputs",
                    "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_match_cost", "lwdetr_match_assign", "lwdetr_match_assign_host",
-                   "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_cocoeval_match", "lwdetr_cocoeval_match_host", "lwdetr_cocoeval_npig",
+                   "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_match_assign_groups", "lwdetr_criterion_train_partials",
+                   "lwdetr_criterion_train_finish", "lwdetr_criterion_backward", "lwdetr_criterion_grad_host", "lwdetr_cocoeval_match", "lwdetr_cocoeval_match_host", "lwdetr_cocoeval_npig",
                    "lwdetr_cocoeval_curves", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
             getattr(l, fn).restype = C.c_int
         _lib = l

@@ -323,7 +323,10 @@ def build(args):
     ``models.lwdetr.SetCriterion`` is importable (i.e. this package is dropped into the reference repository) it is built
     exactly as the reference does, unless ``args.native_criterion`` is true. Otherwise ``criterion`` is this package's
     inference-only ``models.criterion.SetCriterion`` (``engine.evaluate`` runs on it), or ``None`` when ``args`` asks for a
-    loss form it does not implement (``use_varifocal_loss``, ``use_position_supervised_loss``)."""
+    loss form it does not implement (``use_varifocal_loss``, ``use_position_supervised_loss``).
+
+    ``args.native_train_criterion`` (absent or false by default) selects this package's training criterion instead,
+    ``models.criterion_train.TrainSetCriterion``: grouped matching, all four loss forms and gradients, ``train()`` and ``eval()``."""
     num_classes = 20 if args.dataset_file != "coco" else 91
     if args.dataset_file == "o365":
         num_classes = 366
@@ -345,7 +348,11 @@ def build(args):
                    aux_loss=args.aux_loss, group_detr=args.group_detr, two_stage=args.two_stage,
                    lite_refpoint_refine=args.lite_refpoint_refine, bbox_reparam=args.bbox_reparam, args=args)
     model.eval()
-    criterion = None if getattr(args, "native_criterion", False) else _reference_criterion(args, num_classes)
+    if getattr(args, "native_train_criterion", False):
+        from .criterion_train import build_train_criterion
+        criterion = build_train_criterion(args, num_classes)
+    else:
+        criterion = None if getattr(args, "native_criterion", False) else _reference_criterion(args, num_classes)
     if criterion is None:
         from .criterion import build_criterion, native_criterion_supported
         criterion = build_criterion(args, num_classes) if native_criterion_supported(args) else None
