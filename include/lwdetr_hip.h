@@ -31,6 +31,7 @@
  *   lwdetr_match_cost/_assign  models/matcher.py:50-111 (HungarianMatcher.forward: cost matrix, scipy linear_sum_assignment)
  *   lwdetr_criterion_partials/_finish  models/lwdetr.py:256-380, :458-483 (SetCriterion's losses, evaluation only)
  *   lwdetr_cocoeval_match/_npig/_curves  datasets/coco_eval.py:26-78, :219-264 (pycocotools COCOeval for boxes: evaluateImg, accumulate)
+ *   lwdetr_mt_sumsq/_norm_finish/_step  engine.py:76-83 (clip_grad_norm_, torch.optim.AdamW.step, util/utils.py:20-29 ModelEma.update / set)
  */
 #ifndef LWDETR_HIP_H
 #define LWDETR_HIP_H
@@ -594,6 +595,84 @@ int lwdetr_cocoeval_npig(const lwdetr_coco_gt* gt, const int32_t* rows, int n_ro
 int lwdetr_cocoeval_curves(const int64_t* seg_off, const float* score, const int32_t* rank, const int64_t* matched, const int64_t* ignored,
                            const int32_t* npig, const double* rec_thrs, int n_cats, long n_store, double* precision, double* scores,
                            double* recall, void* hip_stream);
+
+/* ---- training-step tail over many tensors: gradient clip, per-tensor AdamW, model EMA (engine.py:76-83: torch.nn.utils.clip_grad_norm_,
+ * torch.optim.AdamW with one parameter group per parameter - util/get_param_dicts.py:53-70 -, util/utils.py:20-29 ModelEma) ----
+ * Two tables in DEVICE memory describe the work (HOST memory for the _host forms and lwdetr_mt_check):
+ *   lwdetr_mt_tensor, one record per tensor: p (the parameter / the model's buffer), g (gradient), m, v (exp_avg, exp_avg_sq), ema (the EMA
+ *     copy's tensor), any of them NULL; numel; kind = LWDETR_MT_PARAM (f32: AdamW, and EMA where ema is set), LWDETR_MT_EMA_F32 (an f32 buffer,
+ *     EMA only), LWDETR_MT_EMA_I64 (an int64 buffer, EMA only: p and ema are int64); skip != 0 for a parameter without a gradient this step;
+ *     the f32 scalars the host computes in double and rounds once, as torch's non-capturable path does: decay_mul = 1 - lr * weight_decay
+ *     (1 where weight_decay = 0), neg_step_size = -(lr / (1 - beta1^t)), bc2_sqrt = sqrt(1 - beta2^t).
+ *   lwdetr_mt_chunk, one per piece of at most LWDETR_MT_CHUNK elements - the work of one wave -: tensor index, element offset, count. The
+ *     chunks tile every tensor exactly once in table order (tensor ascending, offset ascending, every chunk but a tensor's last one full).
+ * lwdetr_mt_check     : that rule on HOST copies of the tables, plus numel > 0, a known kind and element-aligned pointers; LWDETR_ERR_BAD_ARG
+ *                       otherwise. The launch entries cannot read device tables: build the tables on the host, check them once, upload them.
+ *                       Inside the kernels a chunk with a tensor index out of range or a range outside its tensor takes no part (never a
+ *                       truncated or out-of-bounds access).
+ * lwdetr_mt_sumsq     : partials[c] = f32 sum of g^2 over chunk c (0 for a record that is not PARAM, has skip set or no g); (nchunks) f32.
+ * lwdetr_mt_norm_finish : one workgroup adds the partials in f64 in a fixed order; norm_clip (4) f32: [0] = total_norm = (f32) sqrt(sum),
+ *                       [1] = clip_coef = min(1, max_norm / (total_norm + 1e-6)), the quotient in f64 from the unrounded norm, a NaN kept as
+ *                       torch.clamp keeps it; [2] = the part of that f64 coefficient that f32 drops (0 when it clamps to 1); [3] = 0. The step
+ *                       multiplies by [1] + [2] in one fused multiply-add: the clipped gradient is the correctly rounded product, where an
+ *                       f32 coefficient alone costs an ulp that exp_avg_sq doubles. max_norm > 0.
+ * lwdetr_mt_step      : one pass over the chunk table; every array it touches is read once and written once. flags:
+ *     LWDETR_MT_SCALE_GRADS  g *= clip_coef in place (PARAM records with g, without skip). Alone only (LWDETR_ERR_UNSUPPORTED with others).
+ *     LWDETR_MT_ADAMW        PARAM records with p, g, m, v and without skip: gc = g * clip_coef (norm_clip NULL: gc = g);
+ *                            p *= decay_mul; m = lerp(m, gc, 1 - beta1); v = v * beta2 + (1 - beta2) * (gc * gc);
+ *                            p += neg_step_size * (m / (sqrt(v) / bc2_sqrt + eps)). g is NOT written back.
+ *     LWDETR_MT_EMA          every record with p and ema, after the AdamW update of the same element, from registers:
+ *                            e = fl(fl(d e) + fl((1 - d) x)); LWDETR_MT_EMA_I64: (int64) trunc of the same on (float) e, (float) x.
+ *     LWDETR_MT_EMA_SET      e = x (ModelEma.set). Not together with LWDETR_MT_EMA (LWDETR_ERR_BAD_ARG) or LWDETR_MT_ADAMW (UNSUPPORTED).
+ *   hyper (a HOST struct, needed with ADAMW / EMA): the f32 roundings of the doubles 1 - beta1, beta2, 1 - beta2, eps, decay, 1. - decay.
+ *   16-byte accesses where every array of a record that the launch touches is 16-byte aligned, element accesses otherwise.
+ * lwdetr_mt_norm_host / lwdetr_mt_step_host : the same per-lane functions on HOST tables and arrays, lanes and reduction order emulated
+ *                       (sumsq + finish in one call); they run lwdetr_mt_check first.
+ * lwdetr_mt_launch_counts / _name : launches issued and accepted so far by the three device entries (mt_sumsq, mt_norm_finish, mt_step), in
+ *                       the style of lwdetr_gemm_path_counts. LWDETR_ERR_BAD_ARG before any launch: null tables, counts <= 0, bad flags.
+ * No entry synchronises with the host; no floating-point atomics. */
+#define LWDETR_MT_CHUNK 1024
+#define LWDETR_MT_PARAM 0
+#define LWDETR_MT_EMA_F32 1
+#define LWDETR_MT_EMA_I64 2
+#define LWDETR_MT_SCALE_GRADS 1u
+#define LWDETR_MT_ADAMW 2u
+#define LWDETR_MT_EMA 4u
+#define LWDETR_MT_EMA_SET 8u
+typedef struct {
+    void* p;
+    void* g;
+    void* m;
+    void* v;
+    void* ema;
+    int64_t numel;
+    int32_t kind;
+    int32_t skip;
+    float decay_mul;
+    float neg_step_size;
+    float bc2_sqrt;
+    int32_t reserved;
+} lwdetr_mt_tensor;
+typedef struct {
+    int32_t tensor;
+    int32_t count;
+    int64_t offset;
+} lwdetr_mt_chunk;
+typedef struct {
+    float one_minus_beta1, beta2, one_minus_beta2, eps, ema_decay, ema_one_minus_decay;
+} lwdetr_mt_hyper;
+int lwdetr_mt_check(const lwdetr_mt_tensor* tensors, int ntensors, const lwdetr_mt_chunk* chunks, int nchunks);
+int lwdetr_mt_sumsq(const lwdetr_mt_tensor* tensors, int ntensors, const lwdetr_mt_chunk* chunks, int nchunks, float* partials,
+                    void* hip_stream);
+int lwdetr_mt_norm_finish(const float* partials, int nchunks, double max_norm, float* norm_clip, void* hip_stream);
+int lwdetr_mt_step(const lwdetr_mt_tensor* tensors, int ntensors, const lwdetr_mt_chunk* chunks, int nchunks, const lwdetr_mt_hyper* hyper,
+                   unsigned flags, const float* norm_clip, void* hip_stream);
+int lwdetr_mt_norm_host(const lwdetr_mt_tensor* tensors, int ntensors, const lwdetr_mt_chunk* chunks, int nchunks, double max_norm,
+                        float* norm_clip);
+int lwdetr_mt_step_host(const lwdetr_mt_tensor* tensors, int ntensors, const lwdetr_mt_chunk* chunks, int nchunks,
+                        const lwdetr_mt_hyper* hyper, unsigned flags, const float* norm_clip);
+int lwdetr_mt_launch_counts(long* out, int n);
+const char* lwdetr_mt_launch_name(int i);
 
 /* ---- input side: uint8 HWC -> Pillow-exact bilinear square resize -> ToTensor -> Normalize -> NCHW --
  * Replaces datasets/transforms.py:223-231 (SquareResize = PIL.Image.resize((S,S), BILINEAR)), :437-443 (Normalize) and

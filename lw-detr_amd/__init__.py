@@ -23,4 +23,7 @@ def __getattr__(name):
     if name in ("CocoEvaluator", "CocoGroundTruth"):       # the native COCO box evaluator (coco_eval.py), resolved lazily as well
         from . import coco_eval
         return getattr(coco_eval, name)
+    if name == "train":                                    # the training-step tail (train.py): NativeAdamW, ModelEma, clip_grad_norm_, get_param_dict
+        import importlib
+        return importlib.import_module(".train", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -86,6 +86,26 @@ class CocoGt(C.Structure):
                 ("max_group", C.c_int), ("reserved", C.c_int)]
 
 
+MT_CHUNK = 1024
+MT_PARAM, MT_EMA_F32, MT_EMA_I64 = 0, 1, 2
+MT_SCALE_GRADS, MT_ADAMW, MT_EMA, MT_EMA_SET = 1, 2, 4, 8
+
+
+class MtTensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p), ("numel", C.c_int64),
+                ("kind", C.c_int32), ("skip", C.c_int32), ("decay_mul", C.c_float), ("neg_step_size", C.c_float), ("bc2_sqrt", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class MtChunk(C.Structure):
+    _fields_ = [("tensor", C.c_int32), ("count", C.c_int32), ("offset", C.c_int64)]
+
+
+class MtHyper(C.Structure):
+    _fields_ = [("one_minus_beta1", C.c_float), ("beta2", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float),
+                ("ema_decay", C.c_float), ("ema_one_minus_decay", C.c_float)]
+
+
 def is_built() -> bool:
     return os.path.exists(LIB_PATH)
 
@@ -198,6 +218,16 @@ def lib():
         l.lwdetr_cocoeval_match_host.argtypes = [pg, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
         l.lwdetr_cocoeval_npig.argtypes = [pg, vp, i, vp, vp]
         l.lwdetr_cocoeval_curves.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, lg, vp, vp, vp, vp]
+        ph, u = C.POINTER(MtHyper), C.c_uint
+        l.lwdetr_mt_check.argtypes = [vp, i, vp, i]
+        l.lwdetr_mt_sumsq.argtypes = [vp, i, vp, i, vp, vp]
+        l.lwdetr_mt_norm_finish.argtypes = [vp, i, C.c_double, vp, vp]
+        l.lwdetr_mt_step.argtypes = [vp, i, vp, i, ph, u, vp, vp]
+        l.lwdetr_mt_norm_host.argtypes = [vp, i, vp, i, C.c_double, vp]
+        l.lwdetr_mt_step_host.argtypes = [vp, i, vp, i, ph, u, vp]
+        l.lwdetr_mt_launch_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_mt_launch_name.argtypes = [i]
+        l.lwdetr_mt_launch_name.restype = C.c_char_p
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -209,7 +239,8 @@ def lib():
                    "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_match_cost", "lwdetr_match_assign", "lwdetr_match_assign_host",
                    "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_match_assign_groups", "lwdetr_criterion_train_partials",
                    "lwdetr_criterion_train_finish", "lwdetr_criterion_backward", "lwdetr_criterion_grad_host", "lwdetr_cocoeval_match", "lwdetr_cocoeval_match_host", "lwdetr_cocoeval_npig",
-                   "lwdetr_cocoeval_curves", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
+                   "lwdetr_cocoeval_curves", "lwdetr_mt_check", "lwdetr_mt_sumsq", "lwdetr_mt_norm_finish", "lwdetr_mt_step", "lwdetr_mt_norm_host",
+                   "lwdetr_mt_step_host", "lwdetr_mt_launch_counts", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
             getattr(l, fn).restype = C.c_int
         _lib = l
     return _lib
@@ -273,6 +304,15 @@ def attn_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_attn_path_counts(buf, n)
     return {l.lwdetr_attn_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def mt_launch_counts() -> dict:
+    """{entry name: launches so far} of lwdetr_mt_sumsq / lwdetr_mt_norm_finish / lwdetr_mt_step in this process (lwdetr_mt_launch_counts)."""
+    l = lib()
+    n = l.lwdetr_mt_launch_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_mt_launch_counts(buf, n)
+    return {l.lwdetr_mt_launch_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def tuning_set(name: str, value=None):
