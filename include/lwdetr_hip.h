@@ -255,7 +255,10 @@ int lwdetr_ffn_finish(const void* x, long ldx, const float* partial, int splits,
  * Optional chained LayerNorm + QKV of the NEXT block (vit.py:199, :123-130) on the updated rows (needs att != NULL):
  * wqkv_next (3C, C) = next qkv.weight * next norm1.weight[None,:] with the same per-32-chunk column permutation,
  * bqkv_next (3C) f32 = [q_bias, 0, v_bias] + qkv.weight @ norm1.bias; writes Q (pre-scaled by qscale), K as
- * (B, heads, Tp, hd) and V^T as (B, heads, hd, Tp) exactly like lwdetr_gemm's HEADS / HEADS_T epilogues (LN eps = eps_next). */
+ * (B, heads, Tp, hd) and V^T as (B, heads, hd, Tp) exactly like lwdetr_gemm's HEADS / HEADS_T epilogues (LN eps = eps_next).
+ * With the chained QKV, M and Tp must be multiples of 4 (a run of 4 tokens of V^T never crosses an image); M need NOT be a multiple of Tp. Row m goes to
+ * image m / Tp, position m % Tp, so with M % Tp != 0 the last image is partial: its positions M % Tp .. Tp - 1 are not written, and q_out / k_out / vt_out
+ * must hold ceil(M / Tp) whole images (ceil(M / Tp) * Tp * C elements each). The same holds for lwdetr_vit_block_few. */
 int lwdetr_mlp_fused(void* x, long ldx, const void* w1_folded, const float* b1_folded, const void* w2_chunked,
                      const float* b2, const float* gamma2, void* out2, long ld2, float* stats_out, long M, int C,
                      float eps, float eps_next, const void* att, long ldatt, const void* wp, const float* bp,
@@ -316,6 +319,14 @@ const char* lwdetr_msda_path_name(int i);
  * LWDETR_EXPERIMENTS builds only. */
 int lwdetr_attn_path_counts(long* out, int n);
 const char* lwdetr_attn_path_name(int i);
+
+/* The same record for mlp.hip: one counter per kernel instantiation that lwdetr_mlp_fused / lwdetr_vit_block_few / lwdetr_ffn_partial can launch -
+ * mlp_{f16,bf16,f32}_c{192,384}_proj{0,1}_qkv{0,1} (mlp_kernel in ViT mode; proj0_qkv1 does not exist: refused), mlp_small_{f16,bf16}_tt{1,2}_qkv{0,1}_frag{0,1}
+ * (the few-token kernel: 16- / 32-token workgroups, row-major weights through lwdetr_mlp_fused / fragment-major through lwdetr_vit_block_few),
+ * mlp_small_f32_tt1_qkv{0,1}_frag1, vit_few384_{f16,bf16}_qkv{0,1} (counted where lwdetr_vit_block_few hands over to vit_block_few384_kernel),
+ * ffn_{f16,bf16}_c{256,384} (mlp_kernel in FFN mode). lwdetr_ffn_splits is a query and counts nothing. */
+int lwdetr_mlp_path_counts(long* out, int n);
+const char* lwdetr_mlp_path_name(int i);
 long lwdetr_vit_block_stream_bytes(int C, int has_qkv);
 long lwdetr_vit_block_vec_floats(int C);
 int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, const void* wstream, const float* vec, void* out2,

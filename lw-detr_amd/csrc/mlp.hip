@@ -22,7 +22,9 @@
 // LDS row strides are == 2 (mod 4) sixteen-byte slots: conflict-free for the 16-lane ds_read_b128 service groups.
 #include "common.h"
 #include "vit_block_few384.h"
+#include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef MLP_WAVES_PER_SIMD
 #define MLP_WAVES_PER_SIMD 2
@@ -80,6 +82,43 @@ struct MlpParams {
     float* partial; int chunks_per_split;
     int wfrag;                         // few-token kernel: Wp / W1 / Wqkv are fragment-major (lwdetr_vit_block_few)
 };
+
+// ---- launch-form record (lwdetr_mlp_path_counts; modelled on lwdetr_vit_path_counts): one relaxed host counter per kernel instantiation the entries can
+// reach, bumped only when the launch check succeeded (a refused request and the lwdetr_ffn_splits query count nothing; the three mlp_f32_c384 names are always
+// refused, see launch_mlp_p). Counters 0 .. 17: mlp_kernel in ViT
+// mode - (dtype f16 / bf16 / f32) x (C 192 / 384) x (no projection; projection; projection + chained QKV); 18 .. 33: mlp_small_kernel, 16-bit - dtype x TT x QKV x
+// FRAG; 34, 35: its f32 form (TT 1, FRAG); 36 .. 39: vit_block_few384_kernel, counted where lwdetr_vit_block_few hands over to it; 40 .. 43: mlp_kernel in FFN mode.
+constexpr int MP_COUNT = 44;
+std::atomic<long> g_mlp_path[MP_COUNT];
+const char* const kMlpPathNames[MP_COUNT] = {
+    "mlp_f16_c192_proj0_qkv0", "mlp_f16_c192_proj1_qkv0", "mlp_f16_c192_proj1_qkv1", "mlp_f16_c384_proj0_qkv0", "mlp_f16_c384_proj1_qkv0",
+    "mlp_f16_c384_proj1_qkv1", "mlp_bf16_c192_proj0_qkv0", "mlp_bf16_c192_proj1_qkv0", "mlp_bf16_c192_proj1_qkv1", "mlp_bf16_c384_proj0_qkv0",
+    "mlp_bf16_c384_proj1_qkv0", "mlp_bf16_c384_proj1_qkv1", "mlp_f32_c192_proj0_qkv0", "mlp_f32_c192_proj1_qkv0", "mlp_f32_c192_proj1_qkv1",
+    "mlp_f32_c384_proj0_qkv0", "mlp_f32_c384_proj1_qkv0", "mlp_f32_c384_proj1_qkv1", "mlp_small_f16_tt1_qkv0_frag0", "mlp_small_f16_tt1_qkv0_frag1",
+    "mlp_small_f16_tt1_qkv1_frag0", "mlp_small_f16_tt1_qkv1_frag1", "mlp_small_f16_tt2_qkv0_frag0", "mlp_small_f16_tt2_qkv0_frag1", "mlp_small_f16_tt2_qkv1_frag0",
+    "mlp_small_f16_tt2_qkv1_frag1", "mlp_small_bf16_tt1_qkv0_frag0", "mlp_small_bf16_tt1_qkv0_frag1", "mlp_small_bf16_tt1_qkv1_frag0",
+    "mlp_small_bf16_tt1_qkv1_frag1", "mlp_small_bf16_tt2_qkv0_frag0", "mlp_small_bf16_tt2_qkv0_frag1", "mlp_small_bf16_tt2_qkv1_frag0",
+    "mlp_small_bf16_tt2_qkv1_frag1", "mlp_small_f32_tt1_qkv0_frag1", "mlp_small_f32_tt1_qkv1_frag1", "vit_few384_f16_qkv0", "vit_few384_f16_qkv1",
+    "vit_few384_bf16_qkv0", "vit_few384_bf16_qkv1", "ffn_f16_c256", "ffn_f16_c384", "ffn_bf16_c256", "ffn_bf16_c384"};
+template <typename T> constexpr int mp_dt() { return std::is_same<T, f16>::value ? 0 : (std::is_same<T, bf16>::value ? 1 : 2); }
+template <typename T, int C, bool PROJ, bool QKV> constexpr int mp_mlp() {
+    static_assert((C == 192 || C == 384) && (PROJ || !QKV), "a form the record has no name for");
+    return (mp_dt<T>() * 2 + (C == 384 ? 1 : 0)) * 3 + (PROJ ? (QKV ? 2 : 1) : 0);
+}
+template <typename T, bool QKV, int TT, bool FRAG> constexpr int mp_small() {
+    static_assert(TT == 1 || TT == 2, "");
+    static_assert(mp_dt<T>() < 2 || (TT == 1 && FRAG), "the f32 few-token kernel is built with TT = 1 on fragment-major weights only");
+    return mp_dt<T>() == 2 ? 34 + (QKV ? 1 : 0) : 18 + ((mp_dt<T>() * 2 + (TT - 1)) * 2 + (QKV ? 1 : 0)) * 2 + (FRAG ? 1 : 0);
+}
+inline int mp_few384(int dtype, bool qkv) { return 36 + (dtype == DT_F16 ? 0 : 2) + (qkv ? 1 : 0); }
+template <typename T, int C> constexpr int mp_ffn() {
+    static_assert(mp_dt<T>() < 2 && (C == 256 || C == 384), "");
+    return 40 + mp_dt<T>() * 2 + (C == 384 ? 1 : 0);
+}
+inline int mlp_path_done(int path, int rc) {
+    if (rc == LWDETR_OK && path >= 0 && path < MP_COUNT) g_mlp_path[path].fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
 
 template <typename T, int C, int TT, bool PROJ, bool QKV, bool FFN = false>
 __global__ __launch_bounds__(NTHR, MLP_WAVES_PER_SIMD) void mlp_kernel(const MlpParams p) {
@@ -1025,6 +1064,7 @@ __device__ __forceinline__ void mlp_small_f32(const MlpParams& p) {
 template <> __global__ __launch_bounds__(NTHR, 1) void mlp_small_kernel<float, true, 1, true>(const MlpParams p) { mlp_small_f32<true>(p); }
 template <> __global__ __launch_bounds__(NTHR, 1) void mlp_small_kernel<float, false, 1, true>(const MlpParams p) { mlp_small_f32<false>(p); }
 
+constexpr size_t MLP_LDS_MAX = 160 * 1024;         // LDS of a gfx950 CU: the most a workgroup can be given
 constexpr long MLP_SMALL_TT1_MAX_ROWS = 3200;      // one or two 640 x 640 images: 16-token workgroups (see mlp_small_kernel)
 template <typename T, bool QKV, int TT, bool FRAG = false>
 int launch_mlp_small_tt(const MlpParams& p, hipStream_t st) {
@@ -1041,7 +1081,7 @@ int launch_mlp_small_tt(const MlpParams& p, hipStream_t st) {
     const long blocks = (p.M + 16 * TT - 1) / (16 * TT);
     ProfScope ps(KID_MLP, (16.0 + 2.0 + (QKV ? 6.0 : 0.0)) * p.M * C * C, (double)p.M * C * sizeof(T) * 3 + (QKV ? 3.0 : 0.0) * p.M * C * sizeof(T), st);
     hipLaunchKernelGGL((mlp_small_kernel<T, QKV, TT, FRAG>), dim3((unsigned)blocks), dim3(NTHR), lds, st, p);
-    return lwdetr_check_launch();
+    return mlp_path_done(mp_small<T, QKV, TT, FRAG>(), lwdetr_check_launch());
 }
 template <typename T, bool QKV>
 int launch_mlp_small(const MlpParams& p, hipStream_t st) {
@@ -1061,6 +1101,9 @@ int launch_mlp_p(const MlpParams& p, hipStream_t st) {
     constexpr int X1_TILES = 7;
     constexpr size_t x1_b = X1LDS ? (size_t)X1_TILES * 16 * TT * (C + 8) * sizeof(T) : 0;
     constexpr size_t lds = (tiles_b + x1_b > xchg_b ? tiles_b + x1_b : xchg_b) + (9 + (X1LDS ? 2 : 0)) * C * sizeof(float);
+    // float32 at C = 384: two weight-tile buffers alone are 218 KB, more than the 160 KB of a CU. Refused here: hipFuncSetAttribute answers such a size with
+    // hipErrorInvalidValue AND leaves it as the runtime's last error, which the launch check of whatever is launched next would report as its own
+    if constexpr (lds > MLP_LDS_MAX) return LWDETR_ERR_UNSUPPORTED;
     static int ncu_dev[16] = {};               // per device: attribute set + CU count (0 = not initialised)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return LWDETR_ERR_LAUNCH;
@@ -1080,7 +1123,7 @@ int launch_mlp_p(const MlpParams& p, hipStream_t st) {
     ProfScope ps(KID_MLP, (16.0 + (PROJ ? 2.0 : 0.0) + (QKV ? 6.0 : 0.0)) * p.M * C * C,
                  (double)p.M * C * sizeof(T) * (PROJ ? 3 : 2) + (QKV ? 3.0 : 0.0) * p.M * C * sizeof(T), st);
     hipLaunchKernelGGL((mlp_kernel<T, C, TT, PROJ, QKV>), dim3((unsigned)blocks), dim3(NTHR), lds, st, q);
-    return lwdetr_check_launch();
+    return mlp_path_done(mp_mlp<T, C, PROJ, QKV>(), lwdetr_check_launch());
 }
 
 // FFN mode launch: full workgroups (8 tiles each) x S hidden splits, S = the largest power of two that keeps the grid within
@@ -1117,7 +1160,7 @@ int launch_ffn(const MlpParams& p0, int hid, hipStream_t st, int* splits_out) {
     if (splits_out) { *splits_out = S; return LWDETR_OK; }
     ProfScope ps(KID_MLP, 4.0 * p0.M * C * hid, (double)p0.M * C * (sizeof(T) + 4.0 * S) + 2.0 * C * hid * sizeof(T), st);
     hipLaunchKernelGGL((mlp_kernel<T, C, TT, false, false, true>), dim3((unsigned)blocks, (unsigned)S), dim3(NTHR), lds, st, q);
-    return lwdetr_check_launch();
+    return mlp_path_done(mp_ffn<T, C>(), lwdetr_check_launch());
 }
 
 constexpr long MLP_SMALL_MAX_ROWS = 12800;       // below ~8 images the tile-per-workgroup kernel wins (see mlp_small_kernel)
@@ -1215,7 +1258,7 @@ extern "C" int lwdetr_vit_block_few(void* x, long ldx, const void* w1_frag, cons
         f.out2 = out2; f.ld2 = ld2; f.stats_out = stats_out;
         f.wqkv = wqkv_frag_next; f.bqkv = bqkv_next; f.q = q_out; f.k = k_out; f.vt = vt_out; f.qscale = qscale; f.heads = heads; f.hd = hd; f.Tp = Tp;
         f.M = M; f.eps = eps; f.eps_next = eps_next;
-        return lwdetr_vit_block_few384_launch(f, dtype, st);
+        return mlp_path_done(mp_few384(dtype, wqkv_frag_next != nullptr), lwdetr_vit_block_few384_launch(f, dtype, st));
     }
     // f32: 16-token workgroups at every row count - TT = 2 is not built (registers: see mlp_small_f32), so LWDETR_MLP_SMALL_TT is ignored here
     if (dtype == DT_F32) return p.wqkv ? launch_mlp_small_tt<float, true, 1, true>(p, st) : launch_mlp_small_tt<float, false, 1, true>(p, st);
@@ -1257,3 +1300,9 @@ extern "C" int lwdetr_ffn_partial(const void* x, long ldx, const void* w1, const
     if (M == 0) return LWDETR_OK;
     return ffn_entry(x, ldx, w1, b1, w2_chunked, partial, M, C, hid, dtype, hip_stream, nullptr);
 }
+
+extern "C" int lwdetr_mlp_path_counts(long* out, int n) {
+    for (int i = 0; out && i < n && i < MP_COUNT; ++i) out[i] = g_mlp_path[i].load(std::memory_order_relaxed);
+    return MP_COUNT;
+}
+extern "C" const char* lwdetr_mlp_path_name(int i) { return i >= 0 && i < MP_COUNT ? kMlpPathNames[i] : nullptr; }

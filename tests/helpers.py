@@ -239,3 +239,22 @@ def attn_served_by(form, launches=1):
         assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
     else:
         assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"
+
+
+@contextlib.contextmanager
+def mlp_served_by(form, launches=1):
+    """As served_by for the record of mlp.hip (lwdetr_mlp_path_counts): the lwdetr_mlp_fused / lwdetr_vit_block_few / lwdetr_ffn_partial launches inside
+    the block went to exactly the instantiation `form` (a name of lwdetr_mlp_path_name: "mlp_f16_c192_proj1_qkv1", "mlp_small_bf16_tt1_qkv0_frag1",
+    "vit_few384_f16_qkv1", "ffn_bf16_c256", ...), `launches` times (None: at least once), and to no other."""
+    import torch
+    from lwdetr_amd import _native
+    before = _native.mlp_path_counts()
+    assert form in before, f"unknown MLP kernel form {form!r}: {sorted(before)}"
+    yield
+    torch.cuda.synchronize()
+    after = _native.mlp_path_counts()
+    delta = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+    if launches is None:
+        assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
+    else:
+        assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"

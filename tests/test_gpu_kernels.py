@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import attn_served_by, served_by
+from helpers import attn_served_by, mlp_served_by, served_by
 
 pytestmark = pytest.mark.gpu
 
@@ -753,8 +753,10 @@ def test_layernorm_chain_is_bit_identical_to_two_launches(dtype, c):
 def test_ffn_fused(dtype, c, hid, m):
     """Decoder FFN (split-hidden partial products + finishing LayerNorm chain, two launches) vs the torch fp32 formulation
     of transformer.py:507-512 / :397-400 and vs the unfused three-launch plan. 9600 / 19200 = 32 / 64 images x 300 queries
-    (BASELINE configs 2-4), 300 = one image, 40000 = more tiles than one workgroup per CU takes, 64 = a single chunk pair."""
+    (BASELINE configs 2-4), 300 = one image, 40000 = more tiles than one workgroup per CU takes, 64 = a single chunk pair.
+    Each slab element-wise against float64, and the split / tile dealing at its edges: tests/test_gpu_mlp_fp64.py."""
     from lwdetr_amd import kernels as K
+    form = f"ffn_{'f16' if dtype == torch.float16 else 'bf16'}_c{c}"
     assert K.ffn_fused_supported(c, hid, dtype)
     x = _rand(m, c, dtype=dtype, seed=1)
     w1, b1 = _rand(hid, c, scale=c ** -0.5, seed=2), _rand(hid, seed=3) * 0.1
@@ -769,7 +771,8 @@ def test_ffn_fused(dtype, c, hid, m):
     o1, o2 = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
     op = K.FfnOp(x, w1p, b1p, w2c, b2, g1, be1, 1e-5, o1, g2, be2, 1e-5, o2, m, c)
     assert op.splits >= 1 and (hid // 32) % op.splits == 0
-    op()
+    with mlp_served_by(form):
+        op()
     tol = {torch.float16: 4e-3, torch.bfloat16: 3e-2}[dtype]
     assert _relerr(o1, r1) < tol, _relerr(o1, r1)
     assert _relerr(o2, r2) < tol, _relerr(o2, r2)
@@ -781,7 +784,8 @@ def test_ffn_fused(dtype, c, hid, m):
     # in place (the engine's use: out1 aliases x), and deterministic
     xx = x.clone()
     o3 = torch.empty_like(x)
-    K.FfnOp(xx, w1p, b1p, w2c, b2, g1, be1, 1e-5, xx, g2, be2, 1e-5, o3, m, c)()
+    with mlp_served_by(form):
+        K.FfnOp(xx, w1p, b1p, w2c, b2, g1, be1, 1e-5, xx, g2, be2, 1e-5, o3, m, c)()
     assert torch.equal(xx, o1) and torch.equal(o3, o2)
 
 
@@ -791,10 +795,17 @@ def test_mlp_fused(dtype, c, m):
     """LN -> fc1 -> GELU -> fc2 -> LayerScale -> residual in one launch vs the unfused torch fp32 formulation.
     The large M are the BASELINE full sizes (51200 = 32 images x 1600 tokens: 6-7 tiles per workgroup, the LDS-resident
     residual path), a ragged tile count (20000) and more than 7 tiles per CU (64000: extra rounds); 64 / 1000 rows run the
-    few-token kernel with 16-token workgroups, 6400 rows (4 images) with 32-token ones."""
+    few-token kernel with 16-token workgroups, 6400 rows (4 images) with 32-token ones. Which instantiation serves each of the three launches is
+    asserted by the launch-form record; the per-element check of every form is tests/test_gpu_mlp_fp64.py."""
     from lwdetr_amd import kernels as K
     if not K.mlp_fused_supported(c, dtype):
         pytest.skip("not instantiated for this shape / dtype")
+    tname = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}[dtype]
+
+    def form(proj, qkv):      # the form this row count is meant to test: the few-token kernel serves 16-bit C = 192 with the projection below 12800 rows
+        if proj and c == 192 and dtype != torch.float32 and m < 12800:
+            return f"mlp_small_{tname}_tt{1 if m <= 3200 else 2}_qkv{qkv}_frag0"
+        return f"mlp_{tname}_c{c}_proj{proj}_qkv{qkv}"
     x = _rand(m, c, dtype=dtype, seed=1) * 2 + 0.3
     w1, b1 = _rand(4 * c, c, scale=c ** -0.5, seed=2), _rand(4 * c, seed=3) * 0.1
     w2, b2 = _rand(c, 4 * c, scale=(4 * c) ** -0.5, seed=4), _rand(c, seed=5) * 0.1
@@ -805,7 +816,8 @@ def test_mlp_fused(dtype, c, m):
     out2 = torch.zeros(m, 2 * c, dtype=dtype, device=_dev())
     stats = torch.zeros(m, 2, device=_dev())
     xx = x.clone()
-    K.MlpFusedOp(xx, w1f, b1f, w2c, b2, g2, m, c, 1e-6, out2=out2[:, c:], ld2=2 * c, stats_out=stats, eps_next=1e-6)()
+    with mlp_served_by(form(0, 0)):
+        K.MlpFusedOp(xx, w1f, b1f, w2c, b2, g2, m, c, 1e-6, out2=out2[:, c:], ld2=2 * c, stats_out=stats, eps_next=1e-6)()
     tol = {torch.float32: 3e-5, torch.float16: 6e-3, torch.bfloat16: 5e-2}[dtype]
     assert _relerr(xx, ref) < tol, _relerr(xx, ref)
     assert torch.equal(out2[:, c:], xx) and out2[:, :c].abs().max().item() == 0
@@ -820,7 +832,8 @@ def test_mlp_fused(dtype, c, m):
     ref2 = x1r + g2 * (F.gelu(F.layer_norm(x1r, (c,), lw, lb, 1e-6) @ w1.t() + b1) @ w2.t() + b2)
     w1p, b1p, w2p = K.pack_mlp_weights(w1, b1, w2, lw, lb, dtype, proj=True)
     xx = x.clone()
-    K.MlpFusedOp(xx, w1p, b1p, w2p, b2, g2, m, c, 1e-6, att=att, wp=wp.to(dtype).contiguous(), bp=bp, gamma1=g1)()
+    with mlp_served_by(form(1, 0)):
+        K.MlpFusedOp(xx, w1p, b1p, w2p, b2, g2, m, c, 1e-6, att=att, wp=wp.to(dtype).contiguous(), bp=bp, gamma1=g1)()
     assert _relerr(xx, ref2) < tol, _relerr(xx, ref2)
     # ... and with the next block's LayerNorm + QKV chained behind it (Q / K head layout, V transposed)
     heads, hd = 12, c // 12
@@ -835,8 +848,9 @@ def test_mlp_fused(dtype, c, m):
         k = torch.zeros_like(q)
         vt = torch.zeros(nb, heads, hd, tp, dtype=dtype, device=_dev())
         xx2 = x.clone()
-        K.MlpFusedOp(xx2, w1p, b1p, w2p, b2, g2, m, c, 1e-6, att=att, wp=wp.to(dtype).contiguous(), bp=bp, gamma1=g1,
-                     wqkv=wq, bqkv=bq, q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd, Tp=tp)()
+        with mlp_served_by(form(1, 1)):
+            K.MlpFusedOp(xx2, w1p, b1p, w2p, b2, g2, m, c, 1e-6, att=att, wp=wp.to(dtype).contiguous(), bp=bp, gamma1=g1,
+                         wqkv=wq, bqkv=bq, q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd, Tp=tp)()
         assert torch.equal(xx2, xx)
         y = F.layer_norm(xx2.float(), (c,), lw1, lb1, 1e-6) @ wqkv.t() + torch.cat([qb, torch.zeros_like(qb), vb])
         sp = lambda t_: t_.reshape(nb, tp, heads, hd).permute(0, 2, 1, 3)
@@ -850,7 +864,8 @@ def test_mlp_fused(dtype, c, m):
 def test_vit_block_few_fragment_major_weights(dtype, m, tp):
     """lwdetr_vit_block_few (round 6: the few-token ViT block kernel on fragment-major Wp / W1 / Wqkv - pack_frag16) is the arithmetic of
     lwdetr_mlp_fused bit for bit: residual stream, tap copy, row statistics, chained q / k / v^T; also against the torch fp32 formulation.
-    1600 / 3200 rows = one / two 640 x 640 images (16-token workgroups), the rest 32-token workgroups incl. ragged tile counts."""
+    1600 / 3200 rows = one / two 640 x 640 images (16-token workgroups), the rest 32-token workgroups incl. ragged tile counts.
+    The two launches are pinned to their frag0 / frag1 instantiations; against float64 per element at the edge shapes: tests/test_gpu_mlp_fp64.py."""
     from lwdetr_amd import kernels as K
     c, heads = 192, 12
     hd = c // heads
@@ -879,8 +894,9 @@ def test_vit_block_few_fragment_major_weights(dtype, m, tp):
         vt = torch.zeros(nb, heads, hd, tp, dtype=dtype, device=_dev())
         cls = K.VitBlockFewOp if few else K.MlpFusedOp
         f = K.pack_frag16 if few else (lambda t: t)
-        cls(xx, f(w1p), b1p, w2p, b2, g2, m, c, 1e-6, out2=taps[:, c:], ld2=2 * c, stats_out=stats, att=att, wp=f(wpd), bp=bp, gamma1=g1,
-            wqkv=f(wq), bqkv=bq, q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd, Tp=tp)()
+        with mlp_served_by(f"mlp_small_{'f16' if dtype == torch.float16 else 'bf16'}_tt{1 if m <= 3200 else 2}_qkv1_frag{int(few)}"):
+            cls(xx, f(w1p), b1p, w2p, b2, g2, m, c, 1e-6, out2=taps[:, c:], ld2=2 * c, stats_out=stats, att=att, wp=f(wpd), bp=bp, gamma1=g1,
+                wqkv=f(wq), bqkv=bq, q=q, k=k, vt=vt, qscale=0.37, heads=heads, hd=hd, Tp=tp)()
         res.append((xx, taps, stats, q, k, vt))
     for a, b, what in zip(res[1], res[0], "x taps stats q k vt".split()):
         assert torch.equal(a, b), (what, (a.float() - b.float()).abs().max().item())

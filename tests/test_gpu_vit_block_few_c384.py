@@ -2,13 +2,14 @@
 statistics, chained q / k / v^T - under the 16-bit bounds of test_gpu_kernels.py::test_mlp_fused; element-wise against the error of lwdetr_mlp_fused
 at C = 384 (mlp_kernel<T, 384>, row-major weights) on the same operands; determinism; the entry's refusals; and LW-DETR-medium / large in 16-bit with the
 plan switch LWDETR_VIT_BLOCK_FEW_C384 on and unset against the reference goldens. One tile form is built (16 tokens per workgroup), so there is no
-tile-form case."""
+tile-form case. Every launch is pinned to its instantiation by the launch-form record (helpers.mlp_served_by); the per-element bounds are in
+tests/test_gpu_mlp_fp64.py."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import case_batch, golden_state_dict, load_golden
+from helpers import case_batch, golden_state_dict, load_golden, mlp_served_by
 from test_gpu_kernels import _dev, _rand, _relerr
 
 pytestmark = pytest.mark.gpu
@@ -78,7 +79,9 @@ def _run(o, b, *, few=True, qkv=True, extras=True):
         kw.update(out2=b["taps"][:, C:], ld2=2 * C, stats_out=b["stats"])
     if qkv:
         kw.update(wqkv=o["wqF"] if few else o["wq"], bqkv=o["bq"], q=b["q"], k=b["k"], vt=b["vt"], qscale=QSCALE, heads=o["heads"], hd=o["hd"], Tp=o["tp"])
-    cls(b["x"], o["w1F"] if few else o["w1p"], o["b1p"], o["w2p"], o["b2"], o["g2"], o["m"], C, 1e-6, **kw)()
+    name = {F16: "f16", BF16: "bf16"}[o["dtype"]]
+    with mlp_served_by(f"vit_few384_{name}_qkv{int(qkv)}" if few else f"mlp_{name}_c384_proj1_qkv{int(qkv)}"):
+        cls(b["x"], o["w1F"] if few else o["w1p"], o["b1p"], o["w2p"], o["b2"], o["g2"], o["m"], C, 1e-6, **kw)()
     torch.cuda.synchronize()
 
 
@@ -188,7 +191,8 @@ def test_vit_block_few_c384_refusals():
     assert call(c=768, heads=24) == (UNS, True)
     assert call(rows=12800, tp=400) == (UNS, True)
     assert n == m * C
-    rc, same = call()                                                # the control
+    with mlp_served_by("vit_few384_f16_qkv1"):
+        rc, same = call()                                            # the control
     assert rc == 0 and not same
     assert _relerr(xs[:m * C].view(m, C).double(), o["ref"]["x"]) < TOL[F16]
     assert _sentinel(xs[m * C:]) and _sentinel(qs[n:]) and _sentinel(ks[n:]) and _sentinel(vs[n:])

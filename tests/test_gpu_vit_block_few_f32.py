@@ -1,13 +1,14 @@
 """GPU: the float32 form of lwdetr_vit_block_few (mlp_small_kernel<float, QKV, 1, true>, mlp.hip) against float64 - residual stream, tap copy, row
 statistics, chained q / k / v^T - under the float32 bounds of test_gpu_kernels.py::test_mlp_fused; element-wise against the error of today's f32
 lwdetr_mlp_fused kernel on the same operands; determinism; the entry's refusals; and LW-DETR-small / tiny in fp32 with the plan switch
-LWDETR_VIT_BLOCK_FEW_F32 on and unset against the reference goldens. TT = 2 is not built in f32 (LWDETR_MLP_SMALL_TT is ignored), so there is no TT case."""
+LWDETR_VIT_BLOCK_FEW_F32 on and unset against the reference goldens. TT = 2 is not built in f32 (LWDETR_MLP_SMALL_TT is ignored), so there is no TT case.
+Every launch is pinned to its instantiation by the launch-form record (helpers.mlp_served_by); the per-element bounds are in tests/test_gpu_mlp_fp64.py."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import case_batch, golden_state_dict, load_golden
+from helpers import case_batch, golden_state_dict, load_golden, mlp_served_by
 from test_gpu_kernels import _dev, _rand, _relerr
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +76,8 @@ def _run(o, b, *, few=True, qkv=True, extras=True):
         kw.update(out2=b["taps"][:, C:], ld2=2 * C, stats_out=b["stats"])
     if qkv:
         kw.update(wqkv=o["wqF"] if few else o["wq"], bqkv=o["bq"], q=b["q"], k=b["k"], vt=b["vt"], qscale=QSCALE, heads=o["heads"], hd=o["hd"], Tp=o["tp"])
-    cls(b["x"], o["w1F"] if few else o["w1p"], o["b1p"], o["w2p"], o["b2"], o["g2"], o["m"], C, 1e-6, **kw)()
+    with mlp_served_by(f"mlp_small_f32_tt1_qkv{int(qkv)}_frag1" if few else f"mlp_f32_c192_proj1_qkv{int(qkv)}"):
+        cls(b["x"], o["w1F"] if few else o["w1p"], o["b1p"], o["w2p"], o["b2"], o["g2"], o["m"], C, 1e-6, **kw)()
     torch.cuda.synchronize()
 
 
@@ -187,7 +189,8 @@ def test_vit_block_few_f32_refusals():
     assert call(c=384) == (UNS, True)
     assert call(rows=12800, tp=400) == (UNS, True)
     assert n == m * C
-    rc, same = call()                                                # the control
+    with mlp_served_by("mlp_small_f32_tt1_qkv1_frag1"):
+        rc, same = call()                                            # the control
     assert rc == 0 and not same
     assert _relerr(xs[:m * C].view(m, C).double(), o["ref"]["x"]) < 3e-5
     assert _sentinel(xs[m * C:]) and _sentinel(qs[n:])
