@@ -703,6 +703,50 @@ typedef struct {
 int lwdetr_resize_normalize(const lwdetr_resize_image* images, int B, int max_height, const int32_t* tables, uint8_t* tmp,
                             const float* lut, void* out, int S, int dtype, void* hip_stream);
 
+/* ---- training-time input transform (csrc/augment.hip): the reference's train recipes (datasets/coco.py:86-160 over
+ * datasets/transforms.py) per image - RandomHorizontalFlip, then either one resize or RandomResize + RandomSizeCrop + a second
+ * resize - then ToTensor + Normalize, and the zero padding + mask of nested_tensor_from_tensor_list (util/misc.py:317-339), for a
+ * whole batch in at most four launches. Every resize is Pillow's ImagingResample as in lwdetr_resize_normalize (uint8 between passes
+ * and between the two stages; a pass whose input and output lengths are equal is skipped). One descriptor per image:
+ *   src / height / width / row_stride: uint8 RGB rows as in lwdetr_resize_image; flip != 0 reads source column width-1-x (whichever
+ *     pass reads the source does it; no flipped copy exists);
+ *   stage 1 = resize to (h1, w1), then the crop window (top, left, ch, cw) inside it - computed for the window only, with the taps of
+ *     the full w1 / h1 axis at left + x and top + y. An image without a stage 1 carries (h1, w1) = (height, width) and the full window;
+ *   stage 2 = resize of the (ch, cw) window to this image's own (oh, ow);
+ *   row0 / rows: the source rows [row0, row0 + rows) that the stage-1 vertical pass reads for the window - the only rows the stage-1
+ *     horizontal pass computes ((top, ch) when h1 == height);
+ *     with bounds = the height -> h1 table they must be exactly row0 = bounds[top].first and row0 + rows = bounds[top + ch - 1].first +
+ *     bounds[top + ch - 1].count. The entry cannot read the device tables: it checks the range against the image only, and a row0 above
+ *     the first tap of row `top` would make the vertical pass read before its intermediate - the caller computes both from the table it
+ *     uploads, as lwdetr_amd/augment.py does;
+ *   bounds_off / coef_off / ksize [4]: the axis tables in `tables` (int32 elements, layout as lwdetr_resize_image) of width -> w1,
+ *     height -> h1, cw -> ow, ch -> oh; an entry of a skipped pass is not read;
+ *   scratch_off [3]: byte offsets into `scratch` of the uint8 intermediates rows x cw x 3 (after the stage-1 horizontal pass),
+ *     ch x cw x 3 (after the stage-1 vertical pass) and ch x ow x 3 (after the stage-2 horizontal pass); unused ones are not touched.
+ * The horizontal passes read the first and last bytes of a row span as whole aligned 32-bit words: the allocations behind `src` and
+ * `scratch` start and end on 4-byte boundaries (device allocations do).
+ * images_host and images_dev are the same B descriptors in host and in device memory: the host copy is checked and sizes the grids,
+ * the kernels read the device copy. out = (B,3,Hc,Wc) in dtype 0 ... 2 and mask = (B,Hc,Wc) bytes (1 = padding) are written in full:
+ * pixels outside an image's oh x ow are 0 with mask 1. LWDETR_ERR_BAD_ARG for a null pointer, B < 0, a non-positive size, a size above
+ * 65535, row_stride < 3 * width, a zero-sized crop or one outside (h1, w1), (oh, ow) outside (Hc, Wc), source rows outside the image,
+ * a table range outside [0, table_len) or a scratch range outside [0, scratch_bytes); nothing is launched then. B == 0 launches
+ * nothing. */
+typedef struct {
+    const uint8_t* src;
+    int height, width;
+    long row_stride;
+    int flip;
+    int h1, w1;
+    int top, left, ch, cw;
+    int oh, ow;
+    int row0, rows;
+    int bounds_off[4], coef_off[4], ksize[4];
+    long scratch_off[3];
+} lwdetr_augment_image;
+int lwdetr_augment_normalize(const lwdetr_augment_image* images_host, const lwdetr_augment_image* images_dev, int B,
+                             const int32_t* tables, long table_len, uint8_t* scratch, long scratch_bytes, const float* lut,
+                             void* out, uint8_t* mask, int Hc, int Wc, int dtype, void* hip_stream);
+
 /* ---- run-time switches (tuning, A/B runs, tests). Every environment variable LWDETR_<NAME> that a launch path of this library looks at
  * (kernel choices and shapes: ATTN_LDS, ATTN_LDS_CFG, ATTN_SHORT, ATTN_WTILE, ATTN_WIN, ATTN_QT, CHAIN_SPLIT_ROWS, GEMM_BIG, GEMM_BIG_BN, GEMM_BIG_2WG,
  * CONV_PATCH, GEMM_TILE, GEMM_DMA, GEMM_KB, GEMM_NST, GEMM_PT, GEMM_PT_SKEW, MLP_SMALL_TT, FFN_SPLITS, MLP_SMALL, VB_GRID, VB_GELU16, VB_HALF, GEMM_FEW_WAVES) is read

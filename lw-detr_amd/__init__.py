@@ -26,4 +26,7 @@ def __getattr__(name):
     if name == "train":                                    # the training-step tail (train.py): NativeAdamW, ModelEma, clip_grad_norm_, get_param_dict
         import importlib
         return importlib.import_module(".train", __name__)
+    if name == "augment":                                  # the training-time input transforms (augment.py): TrainTransform, sample_train_params, ...
+        import importlib
+        return importlib.import_module(".augment", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

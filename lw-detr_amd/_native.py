@@ -203,6 +203,7 @@ def lib():
         l.lwdetr_postprocess_packed.argtypes = [vp, vp, vp, i, i, i, i, vp, i, vp]
         l.lwdetr_finalize_outputs.argtypes = [vp, vp, lg, vp, lg, vp, lg, i, vp, lg, i, vp]
         l.lwdetr_resize_normalize.argtypes = [vp, i, i, vp, vp, vp, vp, i, i, vp]
+        l.lwdetr_augment_normalize.argtypes = [vp, vp, i, vp, lg, vp, lg, vp, vp, vp, i, i, i, vp]
         pl = C.POINTER(CritLayer)
         l.lwdetr_match_cost.argtypes = [pl, i, i, i, i, vp, vp, vp, vp, f, f, f, f, vp, i, vp]
         l.lwdetr_match_assign.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
@@ -239,7 +240,7 @@ def lib():
         l.lwdetr_prof_collect.argtypes = [vp, vp, vp, vp, i]
         for fn in ("lwdetr_msda_forward", "lwdetr_msda_backward", "lwdetr_msda_fused_forward", "lwdetr_gemm", "lwdetr_attention",
                    "lwdetr_layernorm", "lwdetr_layernorm_chain", "lwdetr_row_stats", "lwdetr_enc_chain", "lwdetr_enc_chain_check", "lwdetr_row_chain", "lwdetr_mlp_fused", "lwdetr_vit_block_few", "lwdetr_vit_block", "lwdetr_vit_qkv", "lwdetr_vit_stem", "lwdetr_ffn_splits", "lwdetr_ffn_partial", "lwdetr_ffn_finish", "lwdetr_select_gather", "lwdetr_decoder_inputs",
-                   "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_match_cost", "lwdetr_match_assign", "lwdetr_match_assign_host",
+                   "lwdetr_box_reparam", "lwdetr_rowmax", "lwdetr_topk", "lwdetr_postprocess", "lwdetr_postprocess_packed", "lwdetr_finalize_outputs", "lwdetr_resize_normalize", "lwdetr_augment_normalize", "lwdetr_match_cost", "lwdetr_match_assign", "lwdetr_match_assign_host",
                    "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_match_assign_groups", "lwdetr_criterion_train_partials",
                    "lwdetr_criterion_train_finish", "lwdetr_criterion_backward", "lwdetr_criterion_grad_host", "lwdetr_cocoeval_match", "lwdetr_cocoeval_match_host", "lwdetr_cocoeval_npig",
                    "lwdetr_cocoeval_curves", "lwdetr_mt_check", "lwdetr_mt_sumsq", "lwdetr_mt_norm_finish", "lwdetr_mt_step", "lwdetr_mt_norm_host",
