@@ -327,6 +327,13 @@ const char* lwdetr_attn_path_name(int i);
  * ffn_{f16,bf16}_c{256,384} (mlp_kernel in FFN mode). lwdetr_ffn_splits is a query and counts nothing. */
 int lwdetr_mlp_path_counts(long* out, int n);
 const char* lwdetr_mlp_path_name(int i);
+
+/* The same record for chain.hip: one counter per kernel instantiation that lwdetr_enc_chain / lwdetr_row_chain can launch, 24 in all -
+ * enc_{f16,bf16}_{d256_pf1,d256_pf0,d384_pf0}_{narrow,wide} (enc_chain_kernel / enc_chain_kernel_wide: pf1 = the cv2 stage in front, k5 = 640;
+ * narrow up to 96 classes, wide up to 384), row_{f16,bf16}_d256_{k512,res0_q0,res1_q0,res1_q1} (the row-per-wave mlp_chain_kernel: k_in = 2 D, or by
+ * whether `res` / `qpos` pointers are GIVEN, used by a stage or not), split_{f16,bf16}_d{256,384} (the channel-split mlp_chain_split_kernel). */
+int lwdetr_chain_path_counts(long* out, int n);
+const char* lwdetr_chain_path_name(int i);
 long lwdetr_vit_block_stream_bytes(int C, int has_qkv);
 long lwdetr_vit_block_vec_floats(int C);
 int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, const void* wstream, const float* vec, void* out2,
@@ -352,8 +359,13 @@ int lwdetr_vit_block(void* x, long ldx, const void* att, long ldatt, const void*
  * ncls < 1 or > 384); the _cls helpers give the sizes for a class count and equal the two older ones up to 96 classes (those keep the
  * narrow form's values). A class count / ld_cls that do not fit are LWDETR_ERR_BAD_ARG before any launch, as every other argument rule;
  * the 2 GB range of the row tensors (LWDETR_ERR_UNSUPPORTED) counts the real ld_cls.
+ * Also LWDETR_ERR_BAD_ARG before any launch: an input row stride shorter than the row, ld_in < (k5 ? k5 : D); a launch whose largest memory row
+ * ((M - 1) / npix) * S + lsi + (M - 1) % npix is not below total_rows (rowvalid / notpad / cls_max are indexed by that row); a null or not 16-byte
+ * aligned values[i], i < nl (`values` is a HOST array; it is read once every other rule has passed).
  * lwdetr_enc_chain_check: the argument checks of lwdetr_enc_chain alone - what it would answer before launching (LWDETR_OK: it would
- * launch, or M == 0); no device call, no pointer is dereferenced. */
+ * launch, or M == 0); no device call, no device pointer is dereferenced; the host array `values` is read (entries [0, nl), after every other rule
+ * has passed) and the check answers for them as the entry does. Both read it guarded: a `values` address that cannot be read is
+ * LWDETR_ERR_BAD_ARG from either, never a fault. */
 long lwdetr_enc_chain_vec_floats(int D, int k5);
 long lwdetr_enc_chain_pieces(int D, int k5, int nl);
 long lwdetr_enc_chain_class_cols(int ncls);
@@ -379,7 +391,11 @@ int lwdetr_enc_chain(const void* in, long ld_in, int k5, void* memory, void* om,
  *   SIDE stage: out[:, 0:n] = W x + b from the current operand (row stride ldo >= ceil4(n); columns up to ceil4(n) are written).
  * in (M, ld_in): k_in channels per row. wstream / vec: lwdetr_amd.kernels.pack_row_chain - 4 KB pieces (32 output channels x 64
  * k-slots in MFMA lane order), stage after stage, + 2 zero pieces; f32 vectors stage after stage: bias (D, or 32 * ceil(n / 32) for a
- * SIDE stage), then gamma (D), beta (D) when LN. */
+ * SIDE stage), then gamma (D), beta (D) when LN.
+ * Row strides: ld_in >= k_in, and ld_res >= D / ld_q >= D for a `res` / `qpos` that is given (all D channels of such a row are loaded whether a stage
+ * uses them or not), each a multiple of 8 with a 16-byte aligned pointer; anything else is LWDETR_ERR_BAD_ARG before any launch. These rules on
+ * in / res / qpos are checked in front of the M == 0 return (LWDETR_OK, nothing launched): they refuse whatever M is. The per-stage rules
+ * (out, ldo, flags) are checked after it, so with M == 0 they are not. */
 enum { LWDETR_CHAIN_FULL = 0, LWDETR_CHAIN_SIDE = 1 };
 enum { LWDETR_CHAIN_RES = 1, LWDETR_CHAIN_RELU = 2, LWDETR_CHAIN_LN = 4, LWDETR_CHAIN_STORE = 8, LWDETR_CHAIN_ADDQ = 16 };
 typedef struct { int kind; int n; int flags; float eps; void* out; long ldo; } lwdetr_chain_stage;

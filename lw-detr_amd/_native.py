@@ -148,6 +148,9 @@ def lib():
         l.lwdetr_mlp_path_counts.argtypes = [C.POINTER(C.c_long), i]
         l.lwdetr_mlp_path_name.argtypes = [i]
         l.lwdetr_mlp_path_name.restype = C.c_char_p
+        l.lwdetr_chain_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_chain_path_name.argtypes = [i]
+        l.lwdetr_chain_path_name.restype = C.c_char_p
         l.lwdetr_attention_tuning.argtypes = [i]
         l.lwdetr_attention_tuning.restype = None
         l.lwdetr_attention_tuning_cfg.argtypes = [i]
@@ -244,7 +247,7 @@ def lib():
                    "lwdetr_criterion_partials", "lwdetr_criterion_finish", "lwdetr_match_assign_groups", "lwdetr_criterion_train_partials",
                    "lwdetr_criterion_train_finish", "lwdetr_criterion_backward", "lwdetr_criterion_grad_host", "lwdetr_cocoeval_match", "lwdetr_cocoeval_match_host", "lwdetr_cocoeval_npig",
                    "lwdetr_cocoeval_curves", "lwdetr_mt_check", "lwdetr_mt_sumsq", "lwdetr_mt_norm_finish", "lwdetr_mt_step", "lwdetr_mt_norm_host",
-                   "lwdetr_mt_step_host", "lwdetr_mt_launch_counts", "lwdetr_mlp_path_counts", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
+                   "lwdetr_mt_step_host", "lwdetr_mt_launch_counts", "lwdetr_mlp_path_counts", "lwdetr_chain_path_counts", "lwdetr_prof_enable", "lwdetr_prof_num_kernels", "lwdetr_prof_collect"):
             getattr(l, fn).restype = C.c_int
         _lib = l
     return _lib
@@ -317,6 +320,15 @@ def mlp_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_mlp_path_counts(buf, n)
     return {l.lwdetr_mlp_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def chain_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_enc_chain / lwdetr_row_chain in this process (lwdetr_chain_path_counts)."""
+    l = lib()
+    n = l.lwdetr_chain_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_chain_path_counts(buf, n)
+    return {l.lwdetr_chain_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def mt_launch_counts() -> dict:

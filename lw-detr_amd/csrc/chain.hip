@@ -14,8 +14,11 @@
 //     per output tile), fragment reads are base + lane * 16 (+ wrapped piece offset): conflict-free, no swizzle.
 // Rounding points are those of the unfused launches (every stage output is rounded to the storage type before it is used again).
 #include "common.h"
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
+#include <unistd.h>
 
 // Phase timing for tuning (tools/chain_timing.py builds a private copy with -DLWDETR_CH_TIMING; never in the product library):
 // s_memrealtime stamps (10 ns ticks) of every wave of the first and the last workgroup of lwdetr_enc_chain at the stage boundaries,
@@ -469,6 +472,38 @@ __global__ __launch_bounds__(256, 1) void mlp_chain_kernel(const MlpChainParams 
     }
 }
 
+// ---- launch-form record (lwdetr_chain_path_counts; modelled on lwdetr_mlp_path_counts): one relaxed host counter per kernel instantiation the two entries
+// can reach, bumped only when the launch check succeeded (a refused request counts nothing). Counters 0 .. 11: enc_chain_kernel / enc_chain_kernel_wide -
+// dtype x (D 256 with cv2 in front; D 256; D 384) x (narrow, wide); 12 .. 19: mlp_chain_kernel<T, 256, KS0, RES, QP> - dtype x (k_in 512; no residual;
+// residual; residual + qpos); 20 .. 23: mlp_chain_split_kernel - dtype x D.
+constexpr int CP_COUNT = 24;
+std::atomic<long> g_chain_path[CP_COUNT];
+const char* const kChainPathNames[CP_COUNT] = {
+    "enc_f16_d256_pf1_narrow", "enc_f16_d256_pf1_wide", "enc_f16_d256_pf0_narrow", "enc_f16_d256_pf0_wide", "enc_f16_d384_pf0_narrow", "enc_f16_d384_pf0_wide",
+    "enc_bf16_d256_pf1_narrow", "enc_bf16_d256_pf1_wide", "enc_bf16_d256_pf0_narrow", "enc_bf16_d256_pf0_wide", "enc_bf16_d384_pf0_narrow",
+    "enc_bf16_d384_pf0_wide", "row_f16_d256_k512", "row_f16_d256_res0_q0", "row_f16_d256_res1_q0", "row_f16_d256_res1_q1", "row_bf16_d256_k512",
+    "row_bf16_d256_res0_q0", "row_bf16_d256_res1_q0", "row_bf16_d256_res1_q1", "split_f16_d256", "split_f16_d384", "split_bf16_d256", "split_bf16_d384"};
+template <typename T> constexpr int cp_dt() {
+    static_assert(std::is_same<T, f16>::value || std::is_same<T, bf16>::value, "16-bit types only");
+    return std::is_same<T, f16>::value ? 0 : 1;
+}
+template <typename T, int D, bool PF, int NCT> constexpr int cp_enc() {
+    static_assert((D == 256 || (D == 384 && !PF)) && (NCT == ENC_NCT_NARROW || NCT == ENC_NCT_WIDE), "a form the record has no name for");
+    return cp_dt<T>() * 6 + (D == 384 ? 2 : PF ? 0 : 1) * 2 + (NCT == ENC_NCT_WIDE ? 1 : 0);
+}
+template <typename T, int D, int KS0, bool RES, bool QP> constexpr int cp_row() {
+    static_assert(D == 256 && (KS0 == D / 16 ? (RES || !QP) : (KS0 == D / 8 && !RES && !QP)), "a form the record has no name for");
+    return 12 + cp_dt<T>() * 4 + (KS0 == D / 8 ? 0 : QP ? 3 : RES ? 2 : 1);
+}
+template <typename T, int D> constexpr int cp_split() {
+    static_assert(D == 256 || D == 384, "");
+    return 20 + cp_dt<T>() * 2 + (D == 384 ? 1 : 0);
+}
+inline int chain_path_done(int path, int rc) {
+    if (rc == LWDETR_OK && path >= 0 && path < CP_COUNT) g_chain_path[path].fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
+
 template <typename T, int D, bool PF, int K5, int NCT>
 int launch_enc(const EncParams& p, hipStream_t st) {
     constexpr int NSLOT = 32;
@@ -489,7 +524,7 @@ int launch_enc(const EncParams& p, hipStream_t st) {
     ProfScope ps(KID_CHAIN, 2.0 * p.M * D * (kin + D + 32.0 * NCT + (double)p.nl * D),
                  (double)p.M * 2.0 * ((PF ? K5 + D : D) + D + 32.0 * NCT + (double)p.nl * D) + 4.0 * p.M, st);
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, st, p);
-    return lwdetr_check_launch();
+    return chain_path_done(cp_enc<T, D, PF, NCT>(), lwdetr_check_launch());
 }
 
 template <typename T, int NCT>
@@ -796,7 +831,7 @@ int launch_mlp_chain_split(const MlpChainParams& p, hipStream_t st, double flops
     }
     ProfScope ps(KID_CHAIN, flops, bytes, st);
     hipLaunchKernelGGL((mlp_chain_split_kernel<T, D>), dim3((unsigned)((p.M + 31) / 32)), dim3(256), lds, st, p);
-    return lwdetr_check_launch();
+    return chain_path_done(cp_split<T, D>(), lwdetr_check_launch());
 }
 
 template <typename T, int D, int KS0, bool RES, bool QP>
@@ -812,7 +847,7 @@ int launch_mlp_chain(const MlpChainParams& p, hipStream_t st, double flops, doub
     }
     ProfScope ps(KID_CHAIN, flops, bytes, st);
     hipLaunchKernelGGL((mlp_chain_kernel<T, D, KS0, RES, QP>), dim3((unsigned)((p.M + 127) / 128)), dim3(256), lds, st, p);
-    return lwdetr_check_launch();
+    return chain_path_done(cp_row<T, D, KS0, RES, QP>(), lwdetr_check_launch());
 }
 
 template <typename T, int D>
@@ -856,6 +891,12 @@ ChainLayout chain_layout(const lwdetr_chain_desc* d) {
 
 }  // namespace
 
+extern "C" int lwdetr_chain_path_counts(long* out, int n) {
+    for (int i = 0; out && i < n && i < CP_COUNT; ++i) out[i] = g_chain_path[i].load(std::memory_order_relaxed);
+    return CP_COUNT;
+}
+extern "C" const char* lwdetr_chain_path_name(int i) { return i >= 0 && i < CP_COUNT ? kChainPathNames[i] : nullptr; }
+
 extern "C" long lwdetr_row_chain_pieces(const lwdetr_chain_desc* d) { const ChainLayout L = chain_layout(d); return L.ok ? L.pieces : -1; }
 extern "C" long lwdetr_row_chain_vec_floats(const lwdetr_chain_desc* d) { const ChainLayout L = chain_layout(d); return L.ok ? L.vec_floats : -1; }
 
@@ -863,9 +904,14 @@ extern "C" int lwdetr_row_chain(const lwdetr_chain_desc* d, int dtype, void* hip
     const ChainLayout L = chain_layout(d);
     if (!L.ok) return LWDETR_ERR_UNSUPPORTED;
     if (!d->in || !d->wstream || !d->vec || d->M < 0 || d->ld_in % 8 != 0 || ((uintptr_t)d->in | (uintptr_t)d->wstream | (uintptr_t)d->vec) % 16 != 0) return LWDETR_ERR_BAD_ARG;
+    // Row strides shorter than the row: rows would overlap and the last rows' loads fall behind the buffer bound (M * ld elements), reading zeros. The kernels
+    // load all D channels of a `res` / `qpos` row that is given, whether a stage uses it or not. Like every rule on in / res / qpos these sit in FRONT of
+    // the M == 0 return: a description with bad row operands is refused whatever M is; the per-stage rules (out, ldo, flags) follow it.
+    if (d->ld_in < d->k_in) return LWDETR_ERR_BAD_ARG;
+    if ((d->res && (d->ld_res % 8 != 0 || d->ld_res < d->D || (uintptr_t)d->res % 16 != 0)) ||
+        (d->qpos && (d->ld_q % 8 != 0 || d->ld_q < d->D || (uintptr_t)d->qpos % 16 != 0))) return LWDETR_ERR_BAD_ARG;
     if (d->M == 0) return LWDETR_OK;
     if (d->k_in != d->D && d->st[0].kind != LWDETR_CHAIN_FULL) return LWDETR_ERR_BAD_ARG;
-    if ((d->res && (d->ld_res % 8 != 0 || (uintptr_t)d->res % 16 != 0)) || (d->qpos && (d->ld_q % 8 != 0 || (uintptr_t)d->qpos % 16 != 0))) return LWDETR_ERR_BAD_ARG;
     MlpChainParams p = {};
     const auto bytes_of = [&](long ld) -> double { return (double)d->M * ld * 2.0; };
     if (bytes_of(d->ld_in) >= 2147483000.0 || (d->res && bytes_of(d->ld_res) >= 2147483000.0) || (d->qpos && bytes_of(d->ld_q) >= 2147483000.0)) return LWDETR_ERR_UNSUPPORTED;
@@ -943,20 +989,52 @@ extern "C" long lwdetr_enc_chain_pieces_cls(int D, int k5, int nl, int ncls) {
     return (k5 ? (long)(D / 32) * (k5 / 64) : 0) + (long)(nl * (D / 32) + D / 32 + cols / 32) * (D / 64) + 2;
 }
 
-// What lwdetr_enc_chain answers for these arguments before it launches anything: the refusal, or LWDETR_OK (it would launch; M == 0: nothing to do).
-// No device call, nothing dereferenced.
-extern "C" int lwdetr_enc_chain_check(const void* in, long ld_in, int k5, void* memory, void* om, void* cls, long ld_cls, float* cls_max,
-                                      void* const* values, int nl, const unsigned char* rowvalid, const unsigned char* notpad,
-                                      const void* wstream, const float* vec, long M, int D, int npix, int S, int lsi, long total_rows,
-                                      int ncls, int dtype) {
+// The argument rules of lwdetr_enc_chain that need no memory access at all (everything but the entries of `values`).
+static int enc_chain_check_args(const void* in, long ld_in, int k5, void* memory, void* om, void* cls, long ld_cls, float* cls_max,
+                                void* const* values, int nl, const unsigned char* rowvalid, const unsigned char* notpad,
+                                const void* wstream, const float* vec, long M, int D, int npix, int S, int lsi, long total_rows,
+                                int ncls, int dtype) {
     if (!in || !om || !cls || !cls_max || !values || !rowvalid || !notpad || !wstream || !vec || M < 0) return LWDETR_ERR_BAD_ARG;
     if (M == 0) return LWDETR_OK;
     const long cols = lwdetr_enc_chain_class_cols(ncls);       // 96 (ld_cls >= 96, as ever) or 384 (ld_cls >= 384)
     if (nl < 1 || nl > 6 || cols < 0 || ld_cls < cols || ld_cls % 8 != 0 || ld_in % 8 != 0 || npix <= 0 || S < npix || lsi < 0) return LWDETR_ERR_BAD_ARG;
     if (k5 && !memory) return LWDETR_ERR_BAD_ARG;
+    // an input row shorter than the channels the kernel contracts over: rows overlap, the last rows' loads fall behind the buffer bound and read zeros
+    if (ld_in < (k5 ? k5 : D)) return LWDETR_ERR_BAD_ARG;
+    // the largest memory row of the launch: the tensor stores are clamped by their buffer descriptors, rowvalid[mm] / notpad[mm] / cls_max[mm] are plain
+    // pointer accesses
+    if ((M - 1) / npix * S + lsi + (M - 1) % npix >= total_rows) return LWDETR_ERR_BAD_ARG;
     if (((uintptr_t)in | (uintptr_t)om | (uintptr_t)cls | (uintptr_t)memory | (uintptr_t)wstream | (uintptr_t)vec) % 16 != 0) return LWDETR_ERR_BAD_ARG;
     if ((double)total_rows * (D > ld_cls ? D : ld_cls) * 2.0 >= 2147483000.0 || (double)M * ld_in * 2.0 >= 2147483000.0) return LWDETR_ERR_UNSUPPORTED;
     if (!((D == 256 && (k5 == 0 || k5 == 640)) || (D == 384 && k5 == 0)) || (dtype != DT_F16 && dtype != DT_BF16)) return LWDETR_ERR_UNSUPPORTED;
+    return LWDETR_OK;
+}
+
+// n bytes of host memory at src -> dst without ever faulting: through a pipe, whose write() answers EFAULT for an address that cannot be read.
+static bool host_copy_checked(const void* src, void* dst, size_t n) {
+    int fd[2];
+    if (pipe(fd) != 0) return false;
+    const bool ok = write(fd[1], src, n) == (ssize_t)n && read(fd[0], dst, n) == (ssize_t)n;
+    close(fd[0]);
+    close(fd[1]);
+    return ok;
+}
+
+// What lwdetr_enc_chain answers for these arguments before it launches anything: the refusal, or LWDETR_OK (it would launch; M == 0: nothing to do).
+// No device call, no device pointer is dereferenced. The HOST array `values` is read, entries [0, nl), once every other rule has passed, as the entry
+// does. Both read it guarded (host_copy_checked, ~3 us): an address that cannot be read is LWDETR_ERR_BAD_ARG from the check AND from the entry, not a
+// fault - callers that ask the check first and the entry second with the same arguments get the same answer whatever `values` is.
+extern "C" int lwdetr_enc_chain_check(const void* in, long ld_in, int k5, void* memory, void* om, void* cls, long ld_cls, float* cls_max,
+                                      void* const* values, int nl, const unsigned char* rowvalid, const unsigned char* notpad,
+                                      const void* wstream, const float* vec, long M, int D, int npix, int S, int lsi, long total_rows,
+                                      int ncls, int dtype) {
+    const int rc = enc_chain_check_args(in, ld_in, k5, memory, om, cls, ld_cls, cls_max, values, nl, rowvalid, notpad, wstream, vec, M, D, npix, S, lsi,
+                                        total_rows, ncls, dtype);
+    if (rc != LWDETR_OK || M == 0) return rc;
+    void* v[6];
+    if (!host_copy_checked(values, v, (size_t)nl * sizeof(void*))) return LWDETR_ERR_BAD_ARG;
+    for (int i = 0; i < nl; ++i)
+        if (!v[i] || (uintptr_t)v[i] % 16 != 0) return LWDETR_ERR_BAD_ARG;
     return LWDETR_OK;
 }
 
@@ -964,14 +1042,16 @@ extern "C" int lwdetr_enc_chain(const void* in, long ld_in, int k5, void* memory
                                 void* const* values, int nl, const unsigned char* rowvalid, const unsigned char* notpad,
                                 const void* wstream, const float* vec, long M, int D, int npix, int S, int lsi, long total_rows,
                                 int ncls, float eps_p, float eps_e, int dtype, void* hip_stream) {
-    const int rc = lwdetr_enc_chain_check(in, ld_in, k5, memory, om, cls, ld_cls, cls_max, values, nl, rowvalid, notpad, wstream, vec, M, D, npix, S, lsi,
-                                          total_rows, ncls, dtype);
+    const int rc = enc_chain_check_args(in, ld_in, k5, memory, om, cls, ld_cls, cls_max, values, nl, rowvalid, notpad, wstream, vec, M, D, npix, S, lsi,
+                                        total_rows, ncls, dtype);
     if (rc != LWDETR_OK || M == 0) return rc;
     EncParams p = {};
     p.in = in; p.ld_in = ld_in; p.memory = k5 ? memory : nullptr; p.om = om; p.cls = cls; p.ld_cls = ld_cls; p.cls_max = cls_max;
+    void* v[6];
+    if (!host_copy_checked(values, v, (size_t)nl * sizeof(void*))) return LWDETR_ERR_BAD_ARG;
     for (int i = 0; i < nl; ++i) {
-        if (!values[i] || (uintptr_t)values[i] % 16 != 0) return LWDETR_ERR_BAD_ARG;
-        p.values[i] = values[i];
+        if (!v[i] || (uintptr_t)v[i] % 16 != 0) return LWDETR_ERR_BAD_ARG;
+        p.values[i] = v[i];
     }
     p.nl = nl; p.rowvalid = rowvalid; p.notpad = notpad; p.wstream = wstream; p.vec = vec;
     p.np = (int)lwdetr_enc_chain_pieces_cls(D, k5, nl, ncls);

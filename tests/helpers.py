@@ -258,3 +258,22 @@ def mlp_served_by(form, launches=1):
         assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
     else:
         assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"
+
+
+@contextlib.contextmanager
+def chain_served_by(form, launches=1):
+    """As served_by for the record of chain.hip (lwdetr_chain_path_counts): the lwdetr_enc_chain / lwdetr_row_chain launches inside the block went to
+    exactly the instantiation `form` (a name of lwdetr_chain_path_name: "enc_f16_d256_pf1_narrow", "row_bf16_d256_res1_q0", "split_f16_d384", ...),
+    `launches` times (None: at least once), and to no other."""
+    import torch
+    from lwdetr_amd import _native
+    before = _native.chain_path_counts()
+    assert form in before, f"unknown chain kernel form {form!r}: {sorted(before)}"
+    yield
+    torch.cuda.synchronize()
+    after = _native.chain_path_counts()
+    delta = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+    if launches is None:
+        assert set(delta) == {form}, f"expected launches of {form} only, the launches went to {delta}"
+    else:
+        assert delta == {form: launches}, f"expected {launches} launch(es) of {form}, the launches went to {delta}"

@@ -133,12 +133,14 @@ def test_packed_sizes_equal_the_helpers(d, k5, ncls):
 
 # ---------------------------------------------------------------------------------------------------------------- (3) refusals before any launch
 BAD_ARG, UNSUPPORTED = -1, -2
+# `values` is a HOST array that the checks read (six dummy device pointers, 16-byte aligned), unlike every other pointer argument
+_VALUES = (C.c_void_p * 6)(*[0x50000 + 0x1000 * i for i in range(6)])
 
 
 def _args(**kw):
     """Arguments lwdetr_enc_chain takes (dummy pointers, every one 16-byte aligned; nothing is dereferenced before the checks are through):
     D = 256 without cv2, 3 layers, one image of 100 tokens, 91 classes in rows of 96."""
-    a = dict(inp=0x10000, ld_in=256, k5=0, memory=None, om=0x20000, cls=0x30000, ld_cls=96, cls_max=0x40000, values=0x50000, nl=3,
+    a = dict(inp=0x10000, ld_in=256, k5=0, memory=None, om=0x20000, cls=0x30000, ld_cls=96, cls_max=0x40000, values=_VALUES, nl=3,
              rowvalid=0x60000, notpad=0x70000, wstream=0x80000, vec=0x90000, M=100, D=256, npix=100, S=100, lsi=0, total_rows=100,
              ncls=91, dtype=1)
     a.update(kw)

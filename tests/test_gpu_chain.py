@@ -6,6 +6,7 @@ import torch
 
 import lwdetr_amd  # noqa: F401
 from lwdetr_amd import kernels as K
+from tests.helpers import chain_served_by
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -52,7 +53,8 @@ def test_enc_chain_matches_torch(d, k5, dtype, B, npix):
     xin = dev(x)
     op = K.EncChainOp(xin, k5 or d, k5, memory if k5 else None, omo, clso, 96, cmax, values, dev(rowvalid), dev(notpad), dev(stream), dev(vec),
                       M=M, d=d, npix=npix, S=S, lsi=0, total_rows=M, ncls=ncls, eps_p=1e-6, eps_e=1e-5)
-    op()
+    with chain_served_by(f"enc_{'f16' if dtype == torch.float16 else 'bf16'}_d{d}_pf{int(bool(k5))}_narrow"):    # (element-wise: test_gpu_chain_fp64.py)
+        op()
     torch.cuda.synchronize()
     ulp = 2.0 ** -10 if dtype == torch.float16 else 2.0 ** -7
 
@@ -104,7 +106,12 @@ def _run_row_chain(d, dtype, k_in, M, stages, res=None, qpos=None, x=None):
     op = K.RowChainOp(dev(x), x.shape[1], k_in, stages, dev(stream), dev(vec), M=M, d=d, res=dev(res), ld_res=d if res is not None else 0,
                       qpos=dev(qpos), ld_q=d if qpos is not None else 0)
     op._hold = (stream, vec)
-    op()
+    name = "f16" if dtype == torch.float16 else "bf16"
+    # up to 16 384 rows (and always at d = 384): 32-row workgroups, channels split over the waves; more rows or k_in = 2 d: a wave per 32 rows
+    split = d == 384 or (k_in == d and M <= 16384)
+    row = "k512" if k_in != d else f"res{int(res is not None)}_q{int(qpos is not None)}"
+    with chain_served_by(f"split_{name}_d{d}" if split else f"row_{name}_d256_{row}"):                             # (element-wise: test_gpu_chain_fp64.py)
+        op()
     torch.cuda.synchronize()
     return outs, refs
 

@@ -14,7 +14,7 @@ import torch
 
 import lwdetr_amd
 from lwdetr_amd import kernels as K
-from helpers import ROOT
+from helpers import ROOT, chain_served_by
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -65,7 +65,9 @@ def _launch(w, x, rowvalid_rows, notpad_rows, d, k5, dtype, nl, ncls, *, B, npix
     op = K.EncChainOp(x.to(DEV), k5 or d, k5, out["memory"] if k5 else None, out["om"], out["cls"], ld_cls, out["cls_max"], out["values"],
                       pad(rowvalid_rows), pad(notpad_rows), stream.to(DEV), vec.to(DEV), M=B * npix, d=d, npix=npix, S=S, lsi=lsi,
                       total_rows=total, ncls=ncls, eps_p=1e-6, eps_e=1e-5)
-    op()
+    form = f"enc_{'f16' if dtype == torch.float16 else 'bf16'}_d{d}_pf{int(bool(k5))}_{'narrow' if ncls <= 96 else 'wide'}"
+    with chain_served_by(form):                                                                                     # (element-wise: test_gpu_chain_fp64.py)
+        op()
     torch.cuda.synchronize()
     return out
 
