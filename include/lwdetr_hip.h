@@ -23,6 +23,7 @@
  *                              layout epilogues fused
  *   lwdetr_attention           models/backbone/vit.py:130-137 (window and global softmax(QK^T)V) and
  *                              models/attention.py:563-606 (decoder self-attention)
+ *   lwdetr_attn_train_forward/_backward  models/backbone/vit.py:130-137 under autograd (training: forward saves lse, backward recomputes p)
  *   lwdetr_mlp_fused           models/backbone/vit.py:217-218 (+ timm.models.layers.Mlp: fc1 -> GELU -> fc2)
  *   lwdetr_vit_block           models/backbone/vit.py:138, :199-218, :123-130 (projection + MLP + next block's norm1 / QKV)
  *   lwdetr_ffn_partial/_finish models/transformer.py:507-512, :397-400 (decoder FFN + norm3 + decoder.norm)
@@ -319,6 +320,37 @@ const char* lwdetr_msda_path_name(int i);
  * LWDETR_EXPERIMENTS builds only. */
 int lwdetr_attn_path_counts(long* out, int n);
 const char* lwdetr_attn_path_name(int i);
+
+/* Differentiable fused attention for training (attention_train.hip; reference models/backbone/vit.py:130-137 under autograd):
+ * o[b,n,h*hd+d] = sum_k softmax_k(scale q[b,n,h,:] . k[b,k,h,:]) v[b,k,h,d], lse[b,h,n] = log sum_k exp(scale q . k) (f32, natural log), no mask.
+ * q, k, v (and dq, dk, dv) are addressed base + b*sb + n*sn + h*sh + d with strides in ELEMENTS and d contiguous, so they may be the views
+ * qkv[:, :, i] of one (B, N, 3, heads, hd) tensor; o (and d_o) is (B, N, heads*hd) with row stride o_ld (do_ld) >= heads*hd; lse is (B, heads, N).
+ * hd in {16, 32, 64}, dtype 0 / 1 / 2, any B, heads, N >= 1. Scores, weights and every sum are f32 in all dtypes (f32 uses the exact
+ * f32-input MFMA); nothing of size N x N is stored. Every element of o, lse, dq, dk, dv is written - the caller pre-zeroes nothing - with no
+ * atomics: two calls on the same inputs give the same bits.
+ * lwdetr_attn_train_backward takes the descriptor of the forward call (q, k, v, the o and lse it wrote), the output gradient d_o and the nine
+ * gradient strides, and needs lwdetr_attn_train_workspace_bytes(...) bytes of 4-byte aligned device scratch (0 for short sequences: workspace
+ * may then be NULL). It computes D = rowsum(d_o o), p = exp(s - lse), dv = p^T d_o, ds = p (d_o v^T - D), dq = scale ds k, dk = scale ds^T q.
+ * LWDETR_ERR_BAD_ARG, before anything is launched: a null pointer, B / heads / N < 1, a scale that is not finite and positive, a tensor
+ * base pointer that is not 16-byte aligned, a stride that is not a multiple of 16 bytes; LWDETR_ERR_UNSUPPORTED: any other hd or dtype.
+ * Launch-form record as lwdetr_attn_path_counts: attn_train_fwd_<dt>_hd<HD>; backward at N <= 256 attn_train_bwd_one_<dt>_hd<HD> (one
+ * launch), above it attn_train_bwd_dot_<dt> + attn_train_bwd_dkdv_<dt>_hd<HD> + attn_train_bwd_dq_<dt>_hd<HD>; <dt> in {f32, f16, bf16}. */
+typedef struct {
+    const void *q, *k, *v;
+    long q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh;
+    void* o;
+    long o_ld;
+    float* lse;
+    int B, heads, N, hd;
+    float scale;
+} lwdetr_attn_train_desc;
+int lwdetr_attn_train_forward(const lwdetr_attn_train_desc* desc, int dtype, void* hip_stream);
+long lwdetr_attn_train_workspace_bytes(int B, int heads, int N, int hd, int dtype);
+int lwdetr_attn_train_backward(const lwdetr_attn_train_desc* desc, const void* d_o, long do_ld, void* dq, void* dk, void* dv,
+                               long dq_sb, long dq_sn, long dq_sh, long dk_sb, long dk_sn, long dk_sh, long dv_sb, long dv_sn, long dv_sh,
+                               void* workspace, int dtype, void* hip_stream);
+int lwdetr_attn_train_path_counts(long* out, int n);
+const char* lwdetr_attn_train_path_name(int i);
 
 /* The same record for mlp.hip: one counter per kernel instantiation that lwdetr_mlp_fused / lwdetr_vit_block_few / lwdetr_ffn_partial can launch -
  * mlp_{f16,bf16,f32}_c{192,384}_proj{0,1}_qkv{0,1} (mlp_kernel in ViT mode; proj0_qkv1 does not exist: refused), mlp_small_{f16,bf16}_tt{1,2}_qkv{0,1}_frag{0,1}

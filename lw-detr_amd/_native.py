@@ -54,6 +54,13 @@ class AttnDesc(C.Structure):
                 ("sub_len", C.c_int), ("kind", C.c_int), ("vt_slack", C.c_int)]
 
 
+class AttnTrainDesc(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("q_sb", C.c_long), ("q_sn", C.c_long), ("q_sh", C.c_long),
+                ("k_sb", C.c_long), ("k_sn", C.c_long), ("k_sh", C.c_long), ("v_sb", C.c_long), ("v_sn", C.c_long), ("v_sh", C.c_long),
+                ("o", C.c_void_p), ("o_ld", C.c_long), ("lse", C.c_void_p), ("B", C.c_int), ("heads", C.c_int), ("N", C.c_int),
+                ("hd", C.c_int), ("scale", C.c_float)]
+
+
 CHAIN_FULL, CHAIN_SIDE = 0, 1
 CHAIN_RES, CHAIN_RELU, CHAIN_LN, CHAIN_STORE, CHAIN_ADDQ = 1, 2, 4, 8, 16
 
@@ -235,6 +242,17 @@ def lib():
         l.lwdetr_mt_launch_counts.argtypes = [C.POINTER(C.c_long), i]
         l.lwdetr_mt_launch_name.argtypes = [i]
         l.lwdetr_mt_launch_name.restype = C.c_char_p
+        pt = C.POINTER(AttnTrainDesc)
+        l.lwdetr_attn_train_forward.argtypes = [pt, i, vp]
+        l.lwdetr_attn_train_forward.restype = C.c_int
+        l.lwdetr_attn_train_workspace_bytes.argtypes = [i, i, i, i, i]
+        l.lwdetr_attn_train_workspace_bytes.restype = C.c_long
+        l.lwdetr_attn_train_backward.argtypes = [pt, vp, lg, vp, vp, vp, lg, lg, lg, lg, lg, lg, lg, lg, lg, vp, i, vp]
+        l.lwdetr_attn_train_backward.restype = C.c_int
+        l.lwdetr_attn_train_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_attn_train_path_counts.restype = C.c_int
+        l.lwdetr_attn_train_path_name.argtypes = [i]
+        l.lwdetr_attn_train_path_name.restype = C.c_char_p
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -311,6 +329,15 @@ def attn_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_attn_path_counts(buf, n)
     return {l.lwdetr_attn_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def attn_train_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_attn_train_forward / lwdetr_attn_train_backward in this process (lwdetr_attn_train_path_counts)."""
+    l = lib()
+    n = l.lwdetr_attn_train_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_attn_train_path_counts(buf, n)
+    return {l.lwdetr_attn_train_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def mlp_path_counts() -> dict:
