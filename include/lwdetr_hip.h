@@ -25,6 +25,7 @@
  *                              models/attention.py:563-606 (decoder self-attention)
  *   lwdetr_attn_train_forward/_backward  models/backbone/vit.py:130-137 under autograd (training: forward saves lse, backward recomputes p)
  *   lwdetr_mlp_fused           models/backbone/vit.py:217-218 (+ timm.models.layers.Mlp: fc1 -> GELU -> fc2)
+ *   lwdetr_msda_train_forward/_backward  models/ops/modules/ms_deform_attn.py:113-142 under autograd (training: nothing saved, no float atomics)
  *   lwdetr_vit_block           models/backbone/vit.py:138, :199-218, :123-130 (projection + MLP + next block's norm1 / QKV)
  *   lwdetr_ffn_partial/_finish models/transformer.py:507-512, :397-400 (decoder FFN + norm3 + decoder.norm)
  *   lwdetr_layernorm           nn.LayerNorm call sites (vit.py:199,:217; transformer.py:231,:499,:511,:516,:398) and
@@ -351,6 +352,57 @@ int lwdetr_attn_train_backward(const lwdetr_attn_train_desc* desc, const void* d
                                void* workspace, int dtype, void* hip_stream);
 int lwdetr_attn_train_path_counts(long* out, int n);
 const char* lwdetr_attn_train_path_name(int i);
+
+/* Differentiable deformable cross-attention for training (msda_train.hip; reference models/ops/modules/ms_deform_attn.py:113-142 between the
+ * Linears, under autograd). With the sampling and border rules of lwdetr_msda_forward above, per (row = b*Q + q, head m), level l, point p:
+ *   loc = ref_xy[row, l] + off / P * ref_wh[row, l] * 0.5,  a = softmax over the L*P logits of (row, m),
+ *   out[b, q, m*D + c] = sum_{l,p} a * bilinear(value[b, level l, m, c], loc).
+ * value: element (b, s, m, c) at value[(b*S + s)*value_ld + m*D + c], value_ld >= M*D in ELEMENTS (a column view of a wider Linear output);
+ * offsets (B*Q, M*L*P*2) and logits (B*Q, M*L*P) with their own leading dimensions in elements; ref (B, Q, L, 4) f32 boxes (cx, cy, w, h) per
+ * level, already multiplied by the valid ratios; mask NULL or (B, S) bytes: a row with a non-zero byte reads as zero and receives a zero
+ * grad_value (masked_fill and its backward); shapes (L, 2) / level_start (L) int64 DEVICE arrays; level_start is arbitrary (gaps allowed; rows
+ * of S that no level covers get a zero grad_value), every level must lie inside [0, S) and hold fewer than 2^30 pixels. value must be finite.
+ * dtype 0 / 1 / 2 (f32 / f16 / bf16) is the type of value, offsets, logits, out, grad_out, grad_value, grad_offsets, grad_logits; all
+ * arithmetic and every sum is f32 (expf and a true division in the softmax, no hardware approximation), each output element is rounded once.
+ * lwdetr_msda_train_forward writes out (B, Q, M*D), contiguous, and saves nothing. lwdetr_msda_train_backward takes the same descriptor,
+ * grad_out (B, Q, M*D) contiguous, and writes EVERY element of grad_value (B, S, M, D) contiguous, grad_offsets (B*Q, M*L*P*2) contiguous,
+ * grad_logits (B*Q, M*L*P) contiguous and grad_ref (B, Q, L, 4) f32 - the caller pre-zeroes nothing:
+ *   d off_x = g_x ref_w 0.5 / P,  d ref_x = sum_{m,p} g_x,  d ref_w = sum_{m,p} g_x off_x 0.5 / P  (y, h alike),  d logit_i = a_i (g_a,i - sum_j a_j g_a,j),
+ * g_x, g_a the location / weight derivatives of lwdetr_msda_backward. It recomputes locations and weights with the forward's functions (same bits)
+ * and needs lwdetr_msda_train_workspace_bytes(desc) bytes of 16-byte aligned device scratch (20 bytes per sample; 0 for a descriptor that would
+ * be refused). No floating-point atomic is used: a second call of either entry on the same inputs returns the same bits, grad_value included.
+ * LWDETR_ERR_BAD_ARG, before anything is launched: a null descriptor or pointer (mask excepted), a size < 1, a leading dimension below its row,
+ * value / out / grad_out / workspace not 16-byte aligned, value_ld not a multiple of 16 bytes, another pointer not aligned to its element, a
+ * workspace that is too small. LWDETR_ERR_UNSUPPORTED, before any runtime call: any other dtype (f64 included), D % 8 != 0, D > 64, L > 4,
+ * P not in {1, 2, 4, 8}, L*P > 16, M > 256. Sizes are checked first, then the supported range, then pointers.
+ * Launch-form record as lwdetr_msda_path_counts: msda_train_fwd_<dt>_<form> and msda_train_bwd_q_<dt>_<form> with <form> in {l1p2, l2p4} (the two
+ * shipped (L, P) pairs, compile-time) or gen (run-time L, P), msda_train_bwd_v_<dt>_e{1,2,4} (D <= 16 / 32 / 64); a backward counts one bwd_q and one bwd_v. */
+typedef struct {
+    const void* value;
+    long value_ld;
+    const void* offsets;
+    long offsets_ld;
+    const void* logits;
+    long logits_ld;
+    const float* ref;
+    const unsigned char* mask;
+    const int64_t* shapes;
+    const int64_t* level_start;
+    int B, S, M, D, L, Q, P, dtype;
+} lwdetr_msda_train_desc;
+int lwdetr_msda_train_forward(const lwdetr_msda_train_desc* desc, void* out, void* hip_stream);
+long lwdetr_msda_train_workspace_bytes(const lwdetr_msda_train_desc* desc);
+int lwdetr_msda_train_backward(const lwdetr_msda_train_desc* desc, const void* grad_out, void* grad_value, void* grad_offsets, void* grad_logits,
+                               float* grad_ref, void* workspace, long workspace_bytes, void* hip_stream);
+/* The backward of ONE (row, head) on HOST arrays in f32, with the per-sample derivative and chain-rule functions the kernels are compiled from
+ * (they are __host__ __device__), so that CPU tests cover the chain rule. value / grad_value point at this image's and head's first channel,
+ * row s at + s*ld; mask NULL or this image's (S) bytes; shapes / level_start host arrays; offsets (L*P*2), logits (L*P), ref (L, 4), grad_out (D).
+ * grad_offsets and grad_logits are written; grad_value and grad_ref (L, 4) are ADDED to (the caller sums heads and rows). Any D >= 1, L*P <= 16. */
+int lwdetr_msda_train_backward_host(const float* value, long value_ld, const unsigned char* mask, const int64_t* shapes, const int64_t* level_start,
+                                    int D, int L, int P, const float* offsets, const float* logits, const float* ref, const float* grad_out,
+                                    float* grad_value, long grad_value_ld, float* grad_offsets, float* grad_logits, float* grad_ref);
+int lwdetr_msda_train_path_counts(long* out, int n);
+const char* lwdetr_msda_train_path_name(int i);
 
 /* The same record for mlp.hip: one counter per kernel instantiation that lwdetr_mlp_fused / lwdetr_vit_block_few / lwdetr_ffn_partial can launch -
  * mlp_{f16,bf16,f32}_c{192,384}_proj{0,1}_qkv{0,1} (mlp_kernel in ViT mode; proj0_qkv1 does not exist: refused), mlp_small_{f16,bf16}_tt{1,2}_qkv{0,1}_frag{0,1}

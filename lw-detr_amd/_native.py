@@ -61,6 +61,12 @@ class AttnTrainDesc(C.Structure):
                 ("hd", C.c_int), ("scale", C.c_float)]
 
 
+class MsdaTrainDesc(C.Structure):
+    _fields_ = [("value", C.c_void_p), ("value_ld", C.c_long), ("offsets", C.c_void_p), ("offsets_ld", C.c_long), ("logits", C.c_void_p),
+                ("logits_ld", C.c_long), ("ref", C.c_void_p), ("mask", C.c_void_p), ("shapes", C.c_void_p), ("level_start", C.c_void_p),
+                ("B", C.c_int), ("S", C.c_int), ("M", C.c_int), ("D", C.c_int), ("L", C.c_int), ("Q", C.c_int), ("P", C.c_int), ("dtype", C.c_int)]
+
+
 CHAIN_FULL, CHAIN_SIDE = 0, 1
 CHAIN_RES, CHAIN_RELU, CHAIN_LN, CHAIN_STORE, CHAIN_ADDQ = 1, 2, 4, 8, 16
 
@@ -253,6 +259,19 @@ def lib():
         l.lwdetr_attn_train_path_counts.restype = C.c_int
         l.lwdetr_attn_train_path_name.argtypes = [i]
         l.lwdetr_attn_train_path_name.restype = C.c_char_p
+        pm = C.POINTER(MsdaTrainDesc)
+        l.lwdetr_msda_train_forward.argtypes = [pm, vp, vp]
+        l.lwdetr_msda_train_forward.restype = C.c_int
+        l.lwdetr_msda_train_workspace_bytes.argtypes = [pm]
+        l.lwdetr_msda_train_workspace_bytes.restype = C.c_long
+        l.lwdetr_msda_train_backward.argtypes = [pm, vp, vp, vp, vp, vp, vp, lg, vp]
+        l.lwdetr_msda_train_backward.restype = C.c_int
+        l.lwdetr_msda_train_backward_host.argtypes = [vp, lg, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, lg, vp, vp, vp]
+        l.lwdetr_msda_train_backward_host.restype = C.c_int
+        l.lwdetr_msda_train_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_msda_train_path_counts.restype = C.c_int
+        l.lwdetr_msda_train_path_name.argtypes = [i]
+        l.lwdetr_msda_train_path_name.restype = C.c_char_p
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -338,6 +357,15 @@ def attn_train_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_attn_train_path_counts(buf, n)
     return {l.lwdetr_attn_train_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def msda_train_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_msda_train_forward / lwdetr_msda_train_backward in this process (lwdetr_msda_train_path_counts)."""
+    l = lib()
+    n = l.lwdetr_msda_train_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_msda_train_path_counts(buf, n)
+    return {l.lwdetr_msda_train_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def mlp_path_counts() -> dict:
