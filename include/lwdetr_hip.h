@@ -404,6 +404,42 @@ int lwdetr_msda_train_backward_host(const float* value, long value_ld, const uns
 int lwdetr_msda_train_path_counts(long* out, int n);
 const char* lwdetr_msda_train_path_name(int i);
 
+/* Two-stage query selection under training (two_stage_train.hip; reference models/transformer.py:224-264 with group_detr groups).
+ * lwdetr_two_stage_scores: for every group g < G and row r < rows (r = b*S + s), in ONE launch,
+ *   x = rowvalid[r] ? memory[r*ld .. + d) : 0,  y = LayerNorm(x W_eo[g]^T + b_eo[g]) * ln_w[g] + ln_b[g] (eps 1e-5),
+ *   scores[g*rows + r] = max_c (y W_cls[g]^T + b_cls[g])_c        (f32; nothing else is written, y and the logits stay on chip).
+ * Weights are stacked over groups and contiguous in `dtype`: w_eo (G, d, d), b_eo / ln_w / ln_b (G, d), w_cls (G, ncls, d), b_cls (G, ncls).
+ * dtype 0 / 1 / 2; products are MFMAs of the input type (f32: the exact 16x16x4 form, no down-conversion), accumulators, LayerNorm and
+ * logits f32; for the 16-bit types y is rounded once, as the operand of the class GEMM. A row's score depends on its values alone, not on its
+ * place in a tile: equal rows (all invalid rows of a group) get equal bits. rows == 0 launches nothing.
+ * lwdetr_two_stage_gather: idx (G, B, nq) int64, distinct inside a (g, b) -> x_sel (B, G, nq, d) = rowvalid ? memory[b, idx] : 0, props_sel
+ *   (B, G, nq, 4) f32 = props[b, idx] (props (B, S, 4) f32), and the inverse table inv (B, S, G) int32 = q where group g selected the row, else
+ *   -1 (every entry is written). An index outside [0, S) selects nothing: zeros, no table entry.
+ * lwdetr_two_stage_scatter_backward: grad_memory (B, S, d) contiguous, every element written: row (b, s) = sum over the groups with
+ *   inv[b, s, g] >= 0 of grad_x_sel[b, g, inv, :], added in ascending g in f32 and rounded once; invalid and unselected rows are zero.
+ * No atomics: a second call returns the same bits.
+ * LWDETR_ERR_UNSUPPORTED: a dtype other than 0 / 1 / 2. LWDETR_ERR_BAD_ARG, before anything is launched: scores - d not 256 / 384, ncls outside
+ * [1, 384], G outside [1, 16], rows < 0, a null pointer, ld < d, memory / weights / d-vectors not 16-byte aligned or ld not a multiple of
+ * 16 bytes; gather / scatter - B, S, nq < 1, nq > S, G outside [1, 16], d outside [1, 4096], a null pointer, ld < d, a pointer not aligned to
+ * its element. The _check entries answer what the entry would answer before launching and touch no device.
+ * Launch-form record as lwdetr_msda_path_counts: ts_scores_<dt>_d{256,384}, ts_gather_<dt>, ts_scatter_<dt>; <dt> in {f32, f16, bf16}. */
+int lwdetr_two_stage_scores(const void* memory, long ld, const unsigned char* rowvalid, const void* w_eo, const void* b_eo, const void* ln_w,
+                            const void* ln_b, const void* w_cls, const void* b_cls, float* scores, long rows, int d, int ncls, int G, int dtype,
+                            void* hip_stream);
+int lwdetr_two_stage_scores_check(const void* memory, long ld, const unsigned char* rowvalid, const void* w_eo, const void* b_eo, const void* ln_w,
+                                  const void* ln_b, const void* w_cls, const void* b_cls, const float* scores, long rows, int d, int ncls, int G,
+                                  int dtype);
+int lwdetr_two_stage_gather(const void* memory, long ld, const unsigned char* rowvalid, const float* props, const int64_t* idx, void* x_sel,
+                            float* props_sel, int* inv, int B, int S, int G, int nq, int d, int dtype, void* hip_stream);
+int lwdetr_two_stage_gather_check(const void* memory, long ld, const unsigned char* rowvalid, const float* props, const int64_t* idx,
+                                  const void* x_sel, const float* props_sel, const int* inv, int B, int S, int G, int nq, int d, int dtype);
+int lwdetr_two_stage_scatter_backward(const void* grad_x_sel, const int* inv, const unsigned char* rowvalid, void* grad_memory, int B, int S, int G,
+                                      int nq, int d, int dtype, void* hip_stream);
+int lwdetr_two_stage_scatter_backward_check(const void* grad_x_sel, const int* inv, const unsigned char* rowvalid, const void* grad_memory, int B,
+                                            int S, int G, int nq, int d, int dtype);
+int lwdetr_two_stage_path_counts(long* out, int n);
+const char* lwdetr_two_stage_path_name(int i);
+
 /* The same record for mlp.hip: one counter per kernel instantiation that lwdetr_mlp_fused / lwdetr_vit_block_few / lwdetr_ffn_partial can launch -
  * mlp_{f16,bf16,f32}_c{192,384}_proj{0,1}_qkv{0,1} (mlp_kernel in ViT mode; proj0_qkv1 does not exist: refused), mlp_small_{f16,bf16}_tt{1,2}_qkv{0,1}_frag{0,1}
  * (the few-token kernel: 16- / 32-token workgroups, row-major weights through lwdetr_mlp_fused / fragment-major through lwdetr_vit_block_few),

@@ -272,6 +272,19 @@ def lib():
         l.lwdetr_msda_train_path_counts.restype = C.c_int
         l.lwdetr_msda_train_path_name.argtypes = [i]
         l.lwdetr_msda_train_path_name.restype = C.c_char_p
+        l.lwdetr_two_stage_scores.argtypes = [vp, lg, vp, vp, vp, vp, vp, vp, vp, vp, lg, i, i, i, i, vp]
+        l.lwdetr_two_stage_scores_check.argtypes = [vp, lg, vp, vp, vp, vp, vp, vp, vp, vp, lg, i, i, i, i]
+        l.lwdetr_two_stage_gather.argtypes = [vp, lg, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        l.lwdetr_two_stage_gather_check.argtypes = [vp, lg, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i]
+        l.lwdetr_two_stage_scatter_backward.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        l.lwdetr_two_stage_scatter_backward_check.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i]
+        for fn in ("lwdetr_two_stage_scores", "lwdetr_two_stage_scores_check", "lwdetr_two_stage_gather", "lwdetr_two_stage_gather_check",
+                   "lwdetr_two_stage_scatter_backward", "lwdetr_two_stage_scatter_backward_check"):
+            getattr(l, fn).restype = C.c_int
+        l.lwdetr_two_stage_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_two_stage_path_counts.restype = C.c_int
+        l.lwdetr_two_stage_path_name.argtypes = [i]
+        l.lwdetr_two_stage_path_name.restype = C.c_char_p
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -366,6 +379,15 @@ def msda_train_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_msda_train_path_counts(buf, n)
     return {l.lwdetr_msda_train_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def two_stage_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_two_stage_scores / _gather / _scatter_backward in this process (lwdetr_two_stage_path_counts)."""
+    l = lib()
+    n = l.lwdetr_two_stage_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_two_stage_path_counts(buf, n)
+    return {l.lwdetr_two_stage_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def mlp_path_counts() -> dict:
