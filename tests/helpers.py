@@ -103,8 +103,14 @@ def oracle_batch(size, batch, res, img_seed, seed=0, chunk=2, forced_topk=None):
     return {k: np.concatenate([p[k] for p in parts], 0) for k in parts[0]}
 
 
+def _collect_numpy(col):
+    """The oracle's collected stages as float32 numpy arrays (batch first), under the oracle's own names."""
+    return {k: v.float().numpy() for k, v in col.items() if k.startswith(("vit.block", "dec.layer")) or k in ("memory", "enc.class_max")}
+
+
 def _oracle_lowp_chunk(job):
-    size, idx, res, img_seed, dtype_name, forced, seed, threads = job
+    size, idx, res, img_seed, dtype_name, forced, seed, threads = job[:8]
+    images, mask, want_col = job[8:] if len(job) > 8 else (None, None, False)
     import torch as _t
     _t.set_num_threads(threads)
     import lwdetr_amd
@@ -114,23 +120,32 @@ def _oracle_lowp_chunk(job):
     cfg = lwdetr_amd.get_args(size)
     model, _, _ = lwdetr_amd.build_model(cfg)
     sd = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in synth_state_dict(model.state_dict(), seed=seed).items()}
-    x = synth_images(max(idx) + 1, res, res, seed=img_seed)[list(idx)].to(dtype)      # counter-based generator: image i is the same in any batch
+    if images is None:
+        x = synth_images(max(idx) + 1, res, res, seed=img_seed)[list(idx)].to(dtype)      # counter-based generator: image i is the same in any batch
+    else:
+        x = _t.from_numpy(images).to(dtype)
+    m = None if mask is None else _t.from_numpy(mask)
     core = O.msda_core
     O.msda_core = lambda value, shapes, loc, aw: core(value.float(), shapes, loc.float(), aw.float()).to(value.dtype)
     try:
         col = {}
         with _t.no_grad():
-            out = O.forward(sd, cfg, x, forced_topk=_t.from_numpy(np.ascontiguousarray(forced)), collect=col)
+            out = O.forward(sd, cfg, x, m, forced_topk=None if forced is None else _t.from_numpy(np.ascontiguousarray(forced)), collect=col)
     finally:
         O.msda_core = core
     f = lambda t: t.float().numpy()
-    return {"pred_logits": f(out["pred_logits"]), "pred_boxes": f(out["pred_boxes"]), "enc_class_max": f(col["enc.class_max"]),
-            "enc_logits": f(out["enc_outputs"]["pred_logits"]), "enc_boxes": f(out["enc_outputs"]["pred_boxes"]),
-            "aux_logits": np.stack([f(a["pred_logits"]) for a in out["aux_outputs"]], 1),
-            "aux_boxes": np.stack([f(a["pred_boxes"]) for a in out["aux_outputs"]], 1)}
+    r = {"pred_logits": f(out["pred_logits"]), "pred_boxes": f(out["pred_boxes"]), "enc_class_max": f(col["enc.class_max"]),
+         "enc_logits": f(out["enc_outputs"]["pred_logits"]), "enc_boxes": f(out["enc_outputs"]["pred_boxes"]),
+         "aux_logits": np.stack([f(a["pred_logits"]) for a in out["aux_outputs"]], 1),
+         "aux_boxes": np.stack([f(a["pred_boxes"]) for a in out["aux_outputs"]], 1)}
+    if images is not None:
+        r["topk_idx"] = out["topk_idx"].numpy()
+    if want_col:
+        r.update({"collect:" + k: v for k, v in _collect_numpy(col).items()})
+    return r
 
 
-def oracle_lowp(size, n, res, img_seed, dtype, forced_topk, seed=0, threads=16, idx=None, chunk=2):
+def oracle_lowp(size, n, res, img_seed, dtype, forced_topk, seed=0, threads=16, idx=None, chunk=2, images=None, mask=None, collect=None):
     """The reference arithmetic IN A 16-BIT DTYPE on the CPU: oracle/lwdetr_torch.py with every parameter
     and the input cast to ``dtype`` - each torch op then rounds its result to that dtype, as the reference does under
     ``model.half()`` / bfloat16 - for images ``idx`` (default: the first ``n``) of synth_images(., res, res, img_seed), with the
@@ -138,21 +153,68 @@ def oracle_lowp(size, n, res, img_seed, dtype, forced_topk, seed=0, threads=16, 
     the 16-bit value / location / weight tensors (CPU grid_sample returns NaN in half precision; the reference's own path casts
     there too, models/transformer.py:356). Images are independent: chunks of ``chunk`` images run in worker processes side by side.
     Returns final + encoder (+ auxiliary) logits / boxes as float32 numpy arrays in the order of ``idx``: their distance to the
-    fp32 oracle is what 16-bit arithmetic itself costs on this network - the yardstick for the HIP path's 16-bit error."""
+    fp32 oracle is what 16-bit arithmetic itself costs on this network - the yardstick for the HIP path's 16-bit error.
+
+    ``images`` (n', 3, H, W) float32 (tensor or numpy), with ``mask`` (n', H, W) bool or None: run on these instead of the synthetic ones
+    (``n``, ``res``, ``img_seed`` and ``idx`` are then unused, ``forced_topk`` (n', nq) goes with the images as given; None = the run's own
+    selection, e.g. with ``dtype`` float32 for the oracle itself) - the result then carries ``topk_idx`` too. ``collect``: a dict that receives the
+    oracle's collected stages (``memory``, ``enc.class_max``, ``vit.block{i}``, ``dec.layer{i}``) as float32 numpy arrays."""
     import multiprocessing as mp
-    idx = list(range(n)) if idx is None else [int(i) for i in idx]
+    if images is None:
+        idx = list(range(n)) if idx is None else [int(i) for i in idx]
+    else:
+        images = np.ascontiguousarray(images.numpy() if isinstance(images, torch.Tensor) else images, dtype=np.float32)
+        mask = None if mask is None else np.ascontiguousarray(mask.numpy() if isinstance(mask, torch.Tensor) else mask, dtype=bool)
+        idx = list(range(images.shape[0]))
     cores = len(os.sched_getaffinity(0))
     groups = [idx[i:i + chunk] for i in range(0, len(idx), chunk)]
     procs = max(1, min(len(groups), cores // 8))
     th = max(1, min(threads, cores // procs))
     name = str(dtype).split(".")[-1]
-    jobs = [(size, g, res, img_seed, name, np.ascontiguousarray(forced_topk[g]), seed, th) for g in groups]
+    fk = lambda g: None if forced_topk is None else np.ascontiguousarray(np.asarray(forced_topk)[g])
+    if images is None and collect is None:
+        jobs = [(size, g, res, img_seed, name, fk(g), seed, th) for g in groups]
+    else:
+        jobs = [(size, g, res, img_seed, name, fk(g), seed, th, None if images is None else images[g],
+                 None if mask is None else mask[g], collect is not None) for g in groups]
     if procs == 1:
         parts = [_oracle_lowp_chunk(j) for j in jobs]
     else:
         with mp.get_context("spawn").Pool(procs) as pool:
             parts = pool.map(_oracle_lowp_chunk, jobs)
-    return {k: np.concatenate([p[k] for p in parts], 0) for k in parts[0]}
+    res_ = {k: np.concatenate([p[k] for p in parts], 0) for k in parts[0]}
+    if collect is not None:
+        collect.update({k[len("collect:"):]: res_[k] for k in res_ if k.startswith("collect:")})
+    return {k: v for k, v in res_.items() if not k.startswith("collect:")}
+
+
+def _oracle_run_job(job):
+    size, images, mask, dtype_name, forced, threads = job
+    import torch as _t
+    col = {}
+    ref = oracle_lowp(size, 0, 0, 0, getattr(_t, dtype_name), forced, threads=threads, images=images, mask=mask, collect=col, chunk=len(images))
+    return ref, col
+
+
+def oracle_run(size, images, mask, dtype, forced_topk=None, threads=16):
+    """oracle_lowp on explicit ``images`` / ``mask`` with its collected stages, in worker processes: (result, collect) of numpy arrays. ``dtype``
+    float32 with ``forced_topk`` None is the fp32 oracle itself (its own two-stage selection, returned as ``topk_idx``); a 16-bit ``dtype`` with the
+    oracle's selection forced is the yardstick. Workers are spawned (the parent may hold a GPU context and its own thread settings): images are
+    independent, so one worker per image where the cores allow (16-bit CPU ops thread poorly)."""
+    import multiprocessing as mp
+    images = np.ascontiguousarray(images.numpy() if isinstance(images, torch.Tensor) else images, dtype=np.float32)
+    mask = None if mask is None else np.ascontiguousarray(mask.numpy() if isinstance(mask, torch.Tensor) else mask, dtype=bool)
+    forced_topk = None if forced_topk is None else np.ascontiguousarray(forced_topk)
+    cores = len(os.sched_getaffinity(0))
+    n = images.shape[0]
+    procs = max(1, min(n, cores // 8))
+    th = max(1, min(threads, cores // procs))
+    name = str(dtype).split(".")[-1]
+    parts = [slice(i, i + 1) for i in range(n)] if procs > 1 else [slice(0, n)]
+    jobs = [(size, images[p], None if mask is None else mask[p], name, None if forced_topk is None else forced_topk[p], th) for p in parts]
+    with mp.get_context("spawn").Pool(procs) as pool:
+        res = pool.map(_oracle_run_job, jobs)
+    return tuple({k: np.concatenate([r[j][k] for r in res], 0) for k in res[0][j]} for j in range(2))
 
 
 def box_iou_xyxy(a, b):
