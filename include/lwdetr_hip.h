@@ -440,6 +440,34 @@ int lwdetr_two_stage_scatter_backward_check(const void* grad_x_sel, const int* i
 int lwdetr_two_stage_path_counts(long* out, int n);
 const char* lwdetr_two_stage_path_name(int i);
 
+/* Training-forward glue (train_glue.hip). dtype 0 / 1 / 2 I/O, f32 arithmetic, one rounding per output element, no floating-point atomic: a
+ * second call returns the same bits.
+ * lwdetr_ln2d_forward: the channels-first LayerNorm of a projector stage (reference models/backbone/projector.py:21-47). x (B, C, HW)
+ *   contiguous; per pixel u = mean_c x, s = mean_c (x - u)^2 (two passes), y = w_c (x - u) / sqrt(s + eps) + b_c. tokens == 0: y (B, C, HW);
+ *   tokens != 0: y (B, HW, C), the rows `memory` is made of. mean / rstd (B, HW) f32 are written for the backward. w, b are f32.
+ * lwdetr_ln2d_backward: dy in the layout of the forward's y -> dx (B, C, HW) in `dtype`, dw / db (C) f32. Every workgroup (64 pixels of one
+ *   image) writes one partial per channel into ws (lwdetr_ln2d_workspace_floats floats) and a second kernel adds them in ascending workgroup
+ *   order.
+ * lwdetr_sine_embed_forward: boxes (rows, 4) with row stride ld (elements) -> out (rows, 4 * dim) contiguous, blocks in the order y, x, w, h
+ *   (box coordinates 1, 0, 2, 3); inside a block element j is sin (even j) or cos (odd j) of 2 pi box_c (inv_hi[j] + inv_lo[j]), where
+ *   inv_hi + inv_lo is 1 / 10000^(2 floor(j / 2) / dim) split into two floats (dim entries each). The argument is reduced in revolutions, so
+ *   the accuracy does not depend on |box|. lwdetr_sine_embed_backward: grad_out (rows, 4 * dim) contiguous -> grad_boxes (rows, 4) contiguous,
+ *   one wave per row, a fixed-order butterfly over the columns. rows == 0 launches nothing.
+ * LWDETR_ERR_UNSUPPORTED: a dtype other than 0 / 1 / 2. LWDETR_ERR_BAD_ARG, before anything is launched: B outside [1, 65535], C outside
+ * [1, 1024], HW < 1, a workspace that is too small, dim odd or outside [2, 256], ld < 4, rows < 0, a null or misaligned pointer.
+ * Launch-form record as lwdetr_msda_path_counts: ln2d_{fwd,bwd}_{nchw,tok}_<dt>, sine_{fwd,bwd}_<dt>; <dt> in {f32, f16, bf16}. */
+int lwdetr_ln2d_forward(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int B, int C, long HW, float eps,
+                        int tokens, int dtype, void* hip_stream);
+long lwdetr_ln2d_workspace_floats(int B, int C, long HW);
+int lwdetr_ln2d_backward(const void* x, const float* w, const float* mean, const float* rstd, const void* dy, void* dx, float* dw, float* db,
+                         float* ws, long ws_floats, int B, int C, long HW, int tokens, int dtype, void* hip_stream);
+int lwdetr_sine_embed_forward(const void* boxes, long ld, const float* inv_hi, const float* inv_lo, void* out, long rows, int dim, int dtype,
+                              void* hip_stream);
+int lwdetr_sine_embed_backward(const void* boxes, long ld, const float* inv_hi, const float* inv_lo, const void* grad_out, void* grad_boxes,
+                               long rows, int dim, int dtype, void* hip_stream);
+int lwdetr_train_glue_path_counts(long* out, int n);
+const char* lwdetr_train_glue_path_name(int i);
+
 /* The same record for mlp.hip: one counter per kernel instantiation that lwdetr_mlp_fused / lwdetr_vit_block_few / lwdetr_ffn_partial can launch -
  * mlp_{f16,bf16,f32}_c{192,384}_proj{0,1}_qkv{0,1} (mlp_kernel in ViT mode; proj0_qkv1 does not exist: refused), mlp_small_{f16,bf16}_tt{1,2}_qkv{0,1}_frag{0,1}
  * (the few-token kernel: 16- / 32-token workgroups, row-major weights through lwdetr_mlp_fused / fragment-major through lwdetr_vit_block_few),

@@ -285,6 +285,20 @@ def lib():
         l.lwdetr_two_stage_path_counts.restype = C.c_int
         l.lwdetr_two_stage_path_name.argtypes = [i]
         l.lwdetr_two_stage_path_name.restype = C.c_char_p
+        l.lwdetr_ln2d_forward.argtypes = [vp, vp, vp, vp, vp, vp, i, i, lg, f, i, i, vp]
+        l.lwdetr_ln2d_forward.restype = C.c_int
+        l.lwdetr_ln2d_workspace_floats.argtypes = [i, i, lg]
+        l.lwdetr_ln2d_workspace_floats.restype = C.c_long
+        l.lwdetr_ln2d_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, lg, i, i, lg, i, i, vp]
+        l.lwdetr_ln2d_backward.restype = C.c_int
+        l.lwdetr_sine_embed_forward.argtypes = [vp, lg, vp, vp, vp, lg, i, i, vp]
+        l.lwdetr_sine_embed_forward.restype = C.c_int
+        l.lwdetr_sine_embed_backward.argtypes = [vp, lg, vp, vp, vp, vp, lg, i, i, vp]
+        l.lwdetr_sine_embed_backward.restype = C.c_int
+        l.lwdetr_train_glue_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_train_glue_path_counts.restype = C.c_int
+        l.lwdetr_train_glue_path_name.argtypes = [i]
+        l.lwdetr_train_glue_path_name.restype = C.c_char_p
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -388,6 +402,15 @@ def two_stage_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_two_stage_path_counts(buf, n)
     return {l.lwdetr_two_stage_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def train_glue_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_ln2d_forward / _backward and lwdetr_sine_embed_forward / _backward in this process (lwdetr_train_glue_path_counts)."""
+    l = lib()
+    n = l.lwdetr_train_glue_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_train_glue_path_counts(buf, n)
+    return {l.lwdetr_train_glue_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def mlp_path_counts() -> dict:

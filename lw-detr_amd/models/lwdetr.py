@@ -48,6 +48,8 @@ class LWDETR(nn.Module):
         self.aux_loss, self.group_detr = aux_loss, group_detr
         self.lite_refpoint_refine, self.bbox_reparam, self.two_stage = lite_refpoint_refine, bbox_reparam, two_stage
         self.transformer.decoder.bbox_embed = None
+        self.transformer.decoder.lite_refpoint_refine, self.transformer.decoder.bbox_reparam = lite_refpoint_refine, bbox_reparam
+        self._drop_path_rate = 0.0
         self.class_embed.bias.data = focal_prior_bias(num_classes)
         nn.init.constant_(self.bbox_embed.layers[-1].weight.data, 0)
         nn.init.constant_(self.bbox_embed.layers[-1].bias.data, 0)
@@ -115,10 +117,20 @@ class LWDETR(nn.Module):
         # chains of a shape together (lwdetr_amd/plan_cache.py; INTEGRATION.md section 6 for the memory this holds)
         return self._plans.get(key, build)
 
-    @torch.no_grad()
     def forward(self, samples, targets=None, _forced_topk=None, _collect=None):
         """samples: NestedTensor | list[Tensor(3,h,w)] | Tensor(B,3,H,W). Returns the reference's output dict:
-        pred_logits (B,nq,C), pred_boxes (B,nq,4) cxcywh, aux_outputs (dec_layers-1 dicts), enc_outputs."""
+        pred_logits (B,nq,C), pred_boxes (B,nq,4) cxcywh, aux_outputs (dec_layers-1 dicts), enc_outputs.
+
+        ``eval()`` runs the HIP launch plan without autograd. ``train()`` runs ``train_forward.differentiable_forward`` with gradients
+        enabled: ``group_detr`` query groups, (B, group_detr * nq, .) outputs, BatchNorm batch statistics; ``targets`` is accepted and
+        ignored, as in the reference."""
+        if self.training:
+            from .train_forward import differentiable_forward
+            return differentiable_forward(self, samples, collect=_collect)
+        with torch.no_grad():
+            return self._forward_plan(samples, _forced_topk, _collect)
+
+    def _forward_plan(self, samples, _forced_topk=None, _collect=None):
         if isinstance(samples, torch.Tensor):
             x, mask = samples, None                     # a dense batch has no padding: no mask work, no host sync
         else:
@@ -233,7 +245,9 @@ class LWDETR(nn.Module):
         return out["pred_boxes"], out["pred_logits"]
 
     def update_drop_path(self, drop_path_rate, vit_encoder_num_layers):
-        pass    # training-only knob of the reference (lwdetr.py:205-210); DropPath is identity at inference
+        # training-only knob of the reference (lwdetr.py:205-210); DropPath is identity at inference. The rate is kept so that the training
+        # forward, which implements no drop-path, can refuse a non-zero one
+        self._drop_path_rate = float(drop_path_rate)
 
     def update_dropout(self, drop_rate):
         for module in self.transformer.modules():

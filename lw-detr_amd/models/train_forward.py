@@ -1,0 +1,199 @@
+"""The differentiable forward of ``LWDETR``: what ``model.train(); model(samples)`` runs.
+
+It restates the reference's forward (``models/lwdetr.py:111-174``, ``backbone/vit.py:343-365``, ``backbone/projector.py:214-241``,
+``backbone/backbone.py:146-159``, ``transformer.py:198-288``) over the parameter containers of ``models/modules.py``, with the fused
+differentiable operators of ``lwdetr_amd.ops`` where the reference has a chain of small launches or keeps large activations:
+
+  ViT attention            ``FusedAttentionFunction`` on the (B', N, 3, heads, hd) view of the qkv Linear's output
+  stage LayerNorm2d        ``layer_norm_2d(tokens=True)``: writes the (B, H*W, C) rows ``memory`` is made of
+  two-stage selection      ``two_stage_select``
+  decoder                  ``decoder_forward``: ``query_sine_embed``, grouped ``fused_attention``, ``FusedMSDeformAttnFunction``
+
+GEMMs, convolutions, BatchNorm, token LayerNorm and GELU are torch operators; the containers' own ``nn.Conv2d`` / ``nn.ConvTranspose2d`` /
+``nn.BatchNorm2d`` / ``nn.Linear`` / ``nn.LayerNorm`` modules are called as modules, so batch statistics, running-statistic updates and a
+``SyncBatchNorm`` conversion behave as in torch.
+
+``fused``: None takes every fused operator whose limits admit the call and whose tensors are on a ROCm device, and the operator's torch
+formulation otherwise; False is all torch, which therefore runs on the CPU and in float64. Drop-path and dropout are not implemented:
+a non-zero rate raises ``NotImplementedError`` in training mode.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from ..ops import attention as A
+from ..ops import decoder_train as D
+from ..ops import train_glue as TG
+from ..ops import two_stage as TS
+from .nested import nested_tensor_from_tensor_list
+
+
+def _unpack(samples):
+    """-> (images (B, 3, H, W), mask (B, H, W) bool or None): a dense batch has no padding."""
+    if isinstance(samples, torch.Tensor):
+        return samples, None
+    if isinstance(samples, (list, tuple)):
+        same = all(t.shape == samples[0].shape for t in samples)
+        samples = nested_tensor_from_tensor_list(list(samples))
+        if same:
+            return samples.tensors, None
+    return samples.tensors, samples.mask
+
+
+def abs_pos(pos_embed, hp, wp):
+    """``get_abs_pos`` (vit.py:26-54) with the class token dropped: (1, 1 + s*s, C) -> (1, hp, wp, C), bicubic when the grid differs."""
+    p = pos_embed[:, 1:]
+    s = int(math.isqrt(p.shape[1]))
+    if (s, s) == (hp, wp):
+        return p.reshape(1, hp, wp, -1)
+    return F.interpolate(p.reshape(1, s, s, -1).permute(0, 3, 1, 2), size=(hp, wp), mode="bicubic", align_corners=False).permute(0, 2, 3, 1)
+
+
+def vit_attention(attn, x, fused=None):
+    """The ViT attention with the cae q / v bias (vit.py:120-140): x (B', N, C) -> (B', N, C)."""
+    b, n, c = x.shape
+    heads = attn.num_heads
+    hd = c // heads
+    bias = torch.cat((attn.q_bias, torch.zeros_like(attn.v_bias), attn.v_bias))
+    qkv = F.linear(x, attn.qkv.weight, bias).reshape(b, n, 3, heads, hd)
+    scale = hd ** -0.5
+    if D._want(fused, qkv.is_cuda and qkv.dtype in A._DTYPES and hd in A._HEAD_DIMS, "vit_attention"):
+        y = A.FusedAttentionFunction.apply(qkv, scale)
+    else:
+        q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)
+        w = ((q * scale) @ k.transpose(-2, -1)).softmax(-1)
+        y = (w @ v).transpose(1, 2).reshape(b, n, c)
+    return attn.proj(y)
+
+
+def vit_forward(enc, images, fused=None):
+    """images (B, 3, H, W) -> the out-feature taps, each (B, C, H/16, W/16) (vit.py:343-365, blocks :195-222)."""
+    x = enc.patch_embed.proj(images).permute(0, 2, 3, 1)
+    b, hp, wp, c = x.shape
+    if hp % 4 or wp % 4:
+        raise RuntimeError(f"lwdetr_amd: the ViT needs a token grid divisible by 4 (image sides divisible by 64), got {hp} x {wp}")
+    x = x + abs_pos(enc.pos_embed, hp, wp).to(x.dtype)
+    h, w = hp // 4, wp // 4
+    x = x.reshape(b, 4, h, 4, w, c).permute(0, 1, 3, 2, 4, 5).reshape(b * 16, h * w, c)
+    taps = []
+    for i, blk in enumerate(enc.blocks):
+        y = blk.norm1(x)
+        if not blk.window:                                          # a global block: the 16 windows of an image are one sequence
+            y = y.reshape(b, 16 * h * w, c)
+        y = vit_attention(blk.attn, y, fused).reshape(b * 16, h * w, c)
+        x = x + blk.gamma_1 * y
+        y = blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(x))))
+        x = x + blk.gamma_2 * y
+        if i in enc.out_feature_indexes:
+            taps.append(x.reshape(b, 4, 4, h, w, c).permute(0, 5, 1, 3, 2, 4).reshape(b, c, hp, wp))
+    return taps
+
+
+def _convx(m, x):
+    x = m.bn(m.conv(x))
+    return F.silu(x) if m.act_name == "silu" else F.relu(x)
+
+
+def _sampling(seq, x):
+    for layer in seq:
+        x = _convx(layer, x) if hasattr(layer, "bn") else layer(x)
+    return x
+
+
+def projector_forward(proj, taps, fused=None):
+    """taps -> per level (tokens (B, h*w, d), (h, w)): resamplers, C2f and the stage LayerNorm2d (projector.py:214-241, :85-132, :21-47)."""
+    levels = []
+    for li, stage in enumerate(proj.stages):
+        feats = [_sampling(proj.stages_sampling[li][ti], t) for ti, t in enumerate(taps)]
+        x = torch.cat(feats, 1) if len(feats) > 1 else feats[0]
+        c2f, ln = stage[0], stage[1]
+        y = _convx(c2f.cv1, x)
+        ys = list(y.split((c2f.c, c2f.c), 1))
+        for m in c2f.m:
+            ys.append(_convx(m.cv2, _convx(m.cv1, ys[-1])))
+        y = _convx(c2f.cv2, torch.cat(ys, 1))
+        if D._want(fused, TG.ln2d_supports(y), "layer_norm_2d"):
+            tok = TG.layer_norm_2d(y, ln.weight, ln.bias, ln.eps, tokens=True)
+        else:
+            tok = TG.layer_norm_2d_torch(y, ln.weight, ln.bias, ln.eps, tokens=True)
+        levels.append((tok, (y.shape[2], y.shape[3])))
+    return levels
+
+
+def two_stage_select_torch(memory, mask_flatten, level_shapes, tr, num_queries, groups):
+    """The reference's own two-stage block (transformer.py:224-264, ``bbox_reparam``) in torch: every token through every group's heads,
+    ``torch.topk``, two gathers. -> (refpoint_ts (detached), memory_ts, boxes_ts, idx (groups, B, nq))."""
+    B, S, d = memory.shape
+    props, valid = TS.proposals(B, level_shapes, mask_flatten, memory.device, unsigmoid=False)
+    props = props.to(memory.dtype)
+    out_mem = memory.masked_fill(~valid.unsqueeze(-1), 0.0)
+    mts, bts, idxs = [], [], []
+    for g in range(groups):
+        y = tr.enc_output_norm[g](tr.enc_output[g](out_mem))
+        cls = tr.enc_out_class_embed[g](y)
+        delta = D.mlp_forward(tr.enc_out_bbox_embed[g], y)
+        coord = torch.cat([delta[..., :2] * props[..., 2:] + props[..., :2], delta[..., 2:].exp() * props[..., 2:]], -1)
+        idx = torch.topk(cls.max(-1)[0], num_queries, dim=1)[1]
+        bts.append(torch.gather(coord, 1, idx.unsqueeze(-1).repeat(1, 1, 4)))
+        mts.append(torch.gather(y, 1, idx.unsqueeze(-1).repeat(1, 1, d)))
+        idxs.append(idx)
+    boxes_ts, memory_ts = torch.cat(bts, 1), torch.cat(mts, 1)
+    return boxes_ts.detach(), memory_ts, boxes_ts, torch.stack(idxs)
+
+
+def _reparam(delta, ref):
+    return torch.cat([delta[..., :2] * ref[..., 2:] + ref[..., :2], delta[..., 2:].exp() * ref[..., 2:]], -1)
+
+
+def _refuse_training_knobs(model):
+    if getattr(model, "_drop_path_rate", 0.0) > 0:
+        raise NotImplementedError(f"lwdetr_amd: drop-path (rate {model._drop_path_rate}) is not implemented in the training forward")
+    D.refuse_dropout(model)
+
+
+def differentiable_forward(model, samples, fused=None, collect=None):
+    """``LWDETR.forward`` with autograd: samples NestedTensor | list[Tensor(3, h, w)] | Tensor(B, 3, H, W) -> the reference's output dict
+    (pred_logits, pred_boxes, aux_outputs, enc_outputs). ``model.training`` selects ``group_detr`` groups and batch statistics; in eval mode
+    one group runs. ``collect`` (a dict) receives ``topk_idx`` (groups, B, nq) and ``memory``."""
+    images, mask = _unpack(samples)
+    if model.training:
+        _refuse_training_knobs(model)
+    groups = model.group_detr if model.training else 1
+    nq, tr = model.num_queries, model.transformer
+    bb = model.backbone[0]
+    levels = projector_forward(bb.projector, vit_forward(bb.encoder, images, fused), fused)
+    level_shapes = [s for _, s in levels]
+    B = images.shape[0]
+    memory = levels[0][0] if len(levels) == 1 else torch.cat([t for t, _ in levels], 1)
+    dev = memory.device
+    mask_flatten = valid_ratios = None
+    if mask is not None:
+        masks = [F.interpolate(mask[None].float(), size=s).to(torch.bool)[0] for s in level_shapes]     # backbone.py:157
+        mask_flatten = torch.cat([m.flatten(1) for m in masks], 1)
+        valid_ratios = torch.stack([TS._valid_ratio(m) for m in masks], 1).to(memory.dtype)
+    spatial_shapes = torch.as_tensor(level_shapes, dtype=torch.long, device=dev)
+    level_start_index = torch.cat((spatial_shapes.new_zeros((1,)), spatial_shapes.prod(1).cumsum(0)[:-1]))
+
+    if D._want(fused, memory.is_cuda and memory.dtype in TS._DTYPES, "two_stage_select"):
+        mem_sel = memory if memory.dtype == tr.enc_output[0].weight.dtype else memory.to(tr.enc_output[0].weight.dtype)
+        refpoint_ts, memory_ts, boxes_ts, idx = TS.two_stage_select(mem_sel, mask_flatten, level_shapes, tr.enc_output, tr.enc_output_norm,
+                                                                    tr.enc_out_class_embed, tr.enc_out_bbox_embed, nq, groups, True,
+                                                                    return_idx=True)
+    else:
+        refpoint_ts, memory_ts, boxes_ts, idx = two_stage_select_torch(memory, mask_flatten, level_shapes, tr, nq, groups)
+    if collect is not None:
+        collect.update(topk_idx=idx, memory=memory)
+
+    tgt = model.query_feat.weight[:groups * nq].unsqueeze(0).repeat(B, 1, 1)
+    refpoint = _reparam(model.refpoint_embed.weight[:groups * nq].unsqueeze(0).repeat(B, 1, 1), refpoint_ts.to(model.refpoint_embed.weight.dtype))
+    hs, ref = D.decoder_forward(tr.decoder, tgt, memory, refpoint, spatial_shapes, level_start_index, valid_ratios, mask_flatten, groups, fused)
+
+    coord = _reparam(D.mlp_forward(model.bbox_embed, hs), ref)
+    cls = model.class_embed(hs)
+    out = {"pred_logits": cls[-1], "pred_boxes": coord[-1]}
+    if model.aux_loss:
+        out["aux_outputs"] = [{"pred_logits": a, "pred_boxes": c} for a, c in zip(cls[:-1], coord[:-1])]
+    cls_enc = torch.cat([tr.enc_out_class_embed[g](t) for g, t in enumerate(memory_ts.split(nq, dim=1))], 1)
+    out["enc_outputs"] = {"pred_logits": cls_enc, "pred_boxes": boxes_ts}
+    return out
