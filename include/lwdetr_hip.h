@@ -468,6 +468,39 @@ int lwdetr_sine_embed_backward(const void* boxes, long ld, const float* inv_hi, 
 int lwdetr_train_glue_path_counts(long* out, int n);
 const char* lwdetr_train_glue_path_name(int i);
 
+/* Stochastic depth on a ViT residual under training (drop_path.hip; reference models/backbone/vit.py:216-220 with timm's DropPath).
+ * lwdetr_drop_path_forward: out[r, c] = x[r, c] + (gamma[c] * y[r, c]) * scale[r / rows_per_group] for r < rows, c < C. scale is f32 with
+ *   rows / rows_per_group entries, each 0 (the group is dropped) or 1 / keep. x and out are in dtype dx, y in dtype dy, gamma f32; every tensor
+ *   has its own leading dimension (elements, at least C). f32 arithmetic in exactly that order, one rounding to dx; in f32 the result is the
+ *   bits of torch's x + (gamma * y) * t. gamma == NULL is the plain x + y * scale. 16-byte accesses when C, the leading dimensions and the
+ *   pointers allow whole 16-byte chunks, element accesses otherwise. A group whose scale is 0 copies x and does not read y: a non-finite y in a
+ *   dropped group does not propagate, where the reference's NaN * 0 would.
+ * lwdetr_drop_path_backward: grad_out (dx) -> grad_y (dy) = (grad_out * scale) * gamma and grad_gamma[c] (f32) = sum_r (grad_out * scale) * y,
+ *   in that order; grad_x is grad_out itself and is not written. Either of grad_y / grad_gamma may be NULL (not both); y is read only for
+ *   grad_gamma, which needs gamma and ws. Every workgroup (16 rows) writes one partial per channel into ws
+ *   (lwdetr_drop_path_workspace_floats(rows, C) floats) and a second kernel adds them in one fixed order (16 interleaved slices of the
+ *   workgroups, each ascending, then the slices in order). No floating-point atomic:
+ *   a second call returns the same bits. A dropped group writes zeros to grad_y and reads neither grad_out nor y.
+ * (dx, dy) in {(0,0), (1,1), (2,2), (0,1), (0,2)}; the last two are what 16-bit autocast hands over. rows == 0 launches nothing.
+ * LWDETR_ERR_UNSUPPORTED: any other dtype pair, C above 2048. LWDETR_ERR_BAD_ARG, before anything is launched: C < 1, rows < 0,
+ * rows_per_group < 1, rows not a multiple of rows_per_group, a null pointer (gamma excepted, and the backward's optional ones as above), a
+ * leading dimension below C, a pointer not aligned to its element, a workspace that is too small, more than 2^31 - 1 workgroups.
+ * lwdetr_drop_path_check answers what the entry would answer before launching and touches no device: backward == 0 with (a, b) = (x, out),
+ * backward != 0 with (a, b) = (grad_out, grad_y).
+ * Launch-form record as lwdetr_msda_path_counts: dp_fwd_<dx>_<dy>, dp_bwd_<dx>_<dy>; <dx>_<dy> in {f32_f32, f16_f16, bf16_bf16, f32_f16,
+ * f32_bf16}. The backward counts once, with or without its second kernel. */
+int lwdetr_drop_path_forward(const void* x, long ldx, const void* y, long ldy, const float* gamma, const float* scale, void* out, long ldo,
+                             long rows, int C, long rows_per_group, int dx, int dy, void* hip_stream);
+long lwdetr_drop_path_workspace_floats(long rows, int C);
+int lwdetr_drop_path_backward(const void* grad_out, long ldg, const void* y, long ldy, const float* gamma, const float* scale, void* grad_y,
+                              long ldgy, float* grad_gamma, float* ws, long ws_floats, long rows, int C, long rows_per_group, int dx, int dy,
+                              void* hip_stream);
+int lwdetr_drop_path_check(int backward, const void* a, long lda, const void* y, long ldy, const float* gamma, const float* scale, const void* b,
+                           long ldb, const float* grad_gamma, const float* ws, long ws_floats, long rows, int C, long rows_per_group, int dx,
+                           int dy);
+int lwdetr_drop_path_path_counts(long* out, int n);
+const char* lwdetr_drop_path_path_name(int i);
+
 /* The same record for mlp.hip: one counter per kernel instantiation that lwdetr_mlp_fused / lwdetr_vit_block_few / lwdetr_ffn_partial can launch -
  * mlp_{f16,bf16,f32}_c{192,384}_proj{0,1}_qkv{0,1} (mlp_kernel in ViT mode; proj0_qkv1 does not exist: refused), mlp_small_{f16,bf16}_tt{1,2}_qkv{0,1}_frag{0,1}
  * (the few-token kernel: 16- / 32-token workgroups, row-major weights through lwdetr_mlp_fused / fragment-major through lwdetr_vit_block_few),

@@ -299,6 +299,18 @@ def lib():
         l.lwdetr_train_glue_path_counts.restype = C.c_int
         l.lwdetr_train_glue_path_name.argtypes = [i]
         l.lwdetr_train_glue_path_name.restype = C.c_char_p
+        l.lwdetr_drop_path_forward.argtypes = [vp, lg, vp, lg, vp, vp, vp, lg, lg, i, lg, i, i, vp]
+        l.lwdetr_drop_path_forward.restype = C.c_int
+        l.lwdetr_drop_path_workspace_floats.argtypes = [lg, i]
+        l.lwdetr_drop_path_workspace_floats.restype = C.c_long
+        l.lwdetr_drop_path_backward.argtypes = [vp, lg, vp, lg, vp, vp, vp, lg, vp, vp, lg, lg, i, lg, i, i, vp]
+        l.lwdetr_drop_path_backward.restype = C.c_int
+        l.lwdetr_drop_path_check.argtypes = [i, vp, lg, vp, lg, vp, vp, vp, lg, vp, vp, lg, lg, i, lg, i, i]
+        l.lwdetr_drop_path_check.restype = C.c_int
+        l.lwdetr_drop_path_path_counts.argtypes = [C.POINTER(C.c_long), i]
+        l.lwdetr_drop_path_path_counts.restype = C.c_int
+        l.lwdetr_drop_path_path_name.argtypes = [i]
+        l.lwdetr_drop_path_path_name.restype = C.c_char_p
         l.lwdetr_tuning_set.argtypes = [C.c_char_p, lg, i]
         l.lwdetr_prof_enable.argtypes = [i]
         l.lwdetr_prof_num_kernels.argtypes = []
@@ -411,6 +423,15 @@ def train_glue_path_counts() -> dict:
     buf = (C.c_long * n)()
     l.lwdetr_train_glue_path_counts(buf, n)
     return {l.lwdetr_train_glue_path_name(i).decode(): int(buf[i]) for i in range(n)}
+
+
+def drop_path_path_counts() -> dict:
+    """{kernel instantiation name: launches so far} of lwdetr_drop_path_forward / _backward in this process (lwdetr_drop_path_path_counts)."""
+    l = lib()
+    n = l.lwdetr_drop_path_path_counts(None, 0)
+    buf = (C.c_long * n)()
+    l.lwdetr_drop_path_path_counts(buf, n)
+    return {l.lwdetr_drop_path_path_name(i).decode(): int(buf[i]) for i in range(n)}
 
 
 def mlp_path_counts() -> dict:

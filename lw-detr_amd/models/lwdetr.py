@@ -245,9 +245,15 @@ class LWDETR(nn.Module):
         return out["pred_boxes"], out["pred_logits"]
 
     def update_drop_path(self, drop_path_rate, vit_encoder_num_layers):
-        # training-only knob of the reference (lwdetr.py:205-210); DropPath is identity at inference. The rate is kept so that the training
-        # forward, which implements no drop-path, can refuse a non-zero one
+        # training-only knob of the reference (lwdetr.py:205-210); DropPath is identity at inference. Only the blocks that were built with a
+        # DropPath container (args.drop_path > 0) take a rate, as in the reference. The rate is kept so that the training forward can refuse a
+        # non-zero one on a model built without the containers, where the reference would silently train without drop-path
         self._drop_path_rate = float(drop_path_rate)
+        dp_rates = [v.item() for v in torch.linspace(0, drop_path_rate, vit_encoder_num_layers)]
+        blocks = self.backbone[0].encoder.blocks
+        for i in range(vit_encoder_num_layers):
+            if hasattr(blocks[i].drop_path, "drop_prob"):
+                blocks[i].drop_path.drop_prob = dp_rates[i]
 
     def update_dropout(self, drop_rate):
         for module in self.transformer.modules():
@@ -348,7 +354,7 @@ def build(args):
         raise NotImplementedError("only the sine position embedding of the published configs is supported")
     backbone = Joiner(
         Backbone(args.encoder, args.vit_encoder_num_layers, args.window_block_indexes, args.hidden_dim,
-                 args.out_feature_indexes, args.projector_scale),
+                 args.out_feature_indexes, args.projector_scale, drop_path=getattr(args, "drop_path", 0.0)),
         PositionEmbeddingSine(args.hidden_dim // 2))
     args.num_feature_levels = len(args.projector_scale)
     transformer = Transformer(

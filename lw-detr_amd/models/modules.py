@@ -39,12 +39,24 @@ class Mlp(_NoCompute):                   # timm.models.layers.Mlp as used by vit
         self.fc2 = nn.Linear(hidden, dim)
 
 
+class DropPath(_NoCompute):
+    """timm's ``DropPath`` as the reference's block holds it (vit.py:182): no parameters, a ``drop_prob`` that ``update_drop_path`` rewrites.
+    The training forward (``train_forward.vit_forward``) reads the rate and applies it on both residuals of the block."""
+
+    def __init__(self, drop_prob=0.0):
+        super().__init__()
+        self.drop_prob = drop_prob
+
+    def extra_repr(self):
+        return f"drop_prob={round(self.drop_prob, 3):0.3f}"
+
+
 class ViTBlock(_NoCompute):              # models/backbone/vit.py:143-193
-    def __init__(self, dim, num_heads, window):
+    def __init__(self, dim, num_heads, window, drop_path=0.0):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
         self.attn = ViTAttention(dim, num_heads)
-        self.drop_path = nn.Identity()
+        self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
         self.mlp = Mlp(dim, dim * 4)
         self.window = window
@@ -59,12 +71,13 @@ class PatchEmbed(_NoCompute):
 
 
 class ViT(_NoCompute):                   # models/backbone/vit.py:225-341
-    def __init__(self, embed_dim, depth, num_heads, window_block_indexes, out_feature_indexes):
+    def __init__(self, embed_dim, depth, num_heads, window_block_indexes, out_feature_indexes, drop_path_rate=0.0):
         super().__init__()
         self.embed_dim, self.depth, self.num_heads = embed_dim, depth, num_heads
         self.patch_embed = PatchEmbed(embed_dim)
         self.pos_embed = nn.Parameter(torch.zeros(1, (224 // 16) ** 2 + 1, embed_dim))
-        self.blocks = nn.ModuleList(ViTBlock(embed_dim, num_heads, i in window_block_indexes) for i in range(depth))
+        dpr = [v.item() for v in torch.linspace(0, drop_path_rate, depth)]     # the stochastic depth decay rule of vit.py:294
+        self.blocks = nn.ModuleList(ViTBlock(embed_dim, num_heads, i in window_block_indexes, dpr[i]) for i in range(depth))
         self.window_block_indexes = list(window_block_indexes)
         idx = [i if i >= 0 else i + depth for i in out_feature_indexes]
         self.out_feature_indexes = [i for i in range(depth) if i in idx]
@@ -149,7 +162,7 @@ class PositionEmbeddingSine(_NoCompute):
 
 
 class Backbone(_NoCompute):              # models/backbone/backbone.py:31-144 (ViT encoders)
-    def __init__(self, name, depth, window_block_indexes, out_channels, out_feature_indexes, projector_scale):
+    def __init__(self, name, depth, window_block_indexes, out_channels, out_feature_indexes, projector_scale, drop_path=0.0):
         super().__init__()
         if name not in VIT_SIZES:
             raise NotImplementedError(f"Backbone {name} is not supported (LW-DETR configs use vit_tiny/small/base)")
@@ -157,7 +170,7 @@ class Backbone(_NoCompute):              # models/backbone/backbone.py:31-144 (V
         assert window_block_indexes is not None and len(projector_scale) > 0
         assert sorted(projector_scale) == list(projector_scale), "projector scales must ascend (P3 < P4 < P5)"
         self.name = name
-        self.encoder = ViT(dim, depth, heads, window_block_indexes, out_feature_indexes)
+        self.encoder = ViT(dim, depth, heads, window_block_indexes, out_feature_indexes, drop_path_rate=drop_path)
         self.projector_scale = list(projector_scale)
         self.projector = MultiScaleProjector(self.encoder._out_feature_channels, out_channels,
                                              [LEVEL_SCALE[l] for l in projector_scale])

@@ -5,6 +5,7 @@ It restates the reference's forward (``models/lwdetr.py:111-174``, ``backbone/vi
 differentiable operators of ``lwdetr_amd.ops`` where the reference has a chain of small launches or keeps large activations:
 
   ViT attention            ``FusedAttentionFunction`` on the (B', N, 3, heads, hd) view of the qkv Linear's output
+  ViT residuals            ``drop_path_residual`` on both residuals of a block whose drop-path rate is above 0, in training mode
   stage LayerNorm2d        ``layer_norm_2d(tokens=True)``: writes the (B, H*W, C) rows ``memory`` is made of
   two-stage selection      ``two_stage_select``
   decoder                  ``decoder_forward``: ``query_sine_embed``, grouped ``fused_attention``, ``FusedMSDeformAttnFunction``
@@ -14,8 +15,16 @@ GEMMs, convolutions, BatchNorm, token LayerNorm and GELU are torch operators; th
 ``SyncBatchNorm`` conversion behave as in torch.
 
 ``fused``: None takes every fused operator whose limits admit the call and whose tensors are on a ROCm device, and the operator's torch
-formulation otherwise; False is all torch, which therefore runs on the CPU and in float64. Drop-path and dropout are not implemented:
-a non-zero rate raises ``NotImplementedError`` in training mode.
+formulation otherwise; False is all torch, which therefore runs on the CPU and in float64.
+
+Drop-path (stochastic depth, the reference's ``--drop_path``): a model built with ``args.drop_path > 0`` holds a ``DropPath`` container in
+every ViT block but the first, with the reference's linspace rates; ``update_drop_path`` rewrites them. In training mode every block with a
+rate above 0 draws one Bernoulli value per WINDOW (B * 16 per draw, as timm's ``DropPath`` does on the (B * 16, h * w, C) view) for the
+attention residual, then one for the MLP residual, blocks in order, from torch's default generator of the tensors' device and in the dtype
+``gamma * y`` has. ``drop_path_keep`` replays a list of masks instead of drawing; the masks used are returned in ``collect``. Blocks with
+rate 0 and eval mode run the plain residual and draw nothing. On a model built with ``args.drop_path == 0`` the reference ignores
+``update_drop_path``; here a non-zero rate on such a model raises ``NotImplementedError`` in training mode. Dropout is not implemented: a
+non-zero rate raises ``NotImplementedError`` in training mode.
 """
 import math
 
@@ -24,6 +33,7 @@ import torch.nn.functional as F
 
 from ..ops import attention as A
 from ..ops import decoder_train as D
+from ..ops import drop_path as DP
 from ..ops import train_glue as TG
 from ..ops import two_stage as TS
 from .nested import nested_tensor_from_tensor_list
@@ -67,8 +77,28 @@ def vit_attention(attn, x, fused=None):
     return attn.proj(y)
 
 
-def vit_forward(enc, images, fused=None):
-    """images (B, 3, H, W) -> the out-feature taps, each (B, C, H/16, W/16) (vit.py:343-365, blocks :195-222)."""
+def _drop_path_residual(x, y, gamma, drop_prob, fused, replay, used):
+    """x + drop_path(gamma * y) (vit.py:216-218) for x, y (B * 16, h * w, C): the mask is drawn as timm draws it, or taken from ``replay``."""
+    if replay is None:
+        keep = DP.drop_path_keep(torch.empty(0, dtype=torch.result_type(gamma, y), device=y.device), x.shape[0], drop_prob)
+    else:
+        keep = next(replay, None)
+        if keep is None:
+            raise ValueError("drop_path_keep holds fewer masks than the forward draws (two per block with a drop-path rate above 0)")
+        keep = torch.as_tensor(keep).to(device=y.device, dtype=torch.bool)
+        if tuple(keep.shape) != (x.shape[0],):
+            raise ValueError(f"drop_path_keep: a mask of shape {tuple(keep.shape)}, expected ({x.shape[0]},) - one entry per window")
+    used.append(keep)
+    if D._want(fused, DP.drop_path_supports(x, y, gamma), "drop_path_residual"):
+        return DP.drop_path_residual(x, y, gamma, keep, drop_prob)
+    return DP.drop_path_residual_torch(x, y, gamma, keep, drop_prob)
+
+
+def vit_forward(enc, images, fused=None, training=False, drop_path_keep=None, used_keep=None):
+    """images (B, 3, H, W) -> the out-feature taps, each (B, C, H/16, W/16) (vit.py:343-365, blocks :195-222). ``training``: blocks whose
+    ``drop_path.drop_prob`` is above 0 drop windows on both residuals; ``drop_path_keep`` (an iterator of bool (B * 16,) masks) replaces the
+    draws, ``used_keep`` (a list) receives the masks in draw order."""
+    used_keep = [] if used_keep is None else used_keep
     x = enc.patch_embed.proj(images).permute(0, 2, 3, 1)
     b, hp, wp, c = x.shape
     if hp % 4 or wp % 4:
@@ -82,9 +112,16 @@ def vit_forward(enc, images, fused=None):
         if not blk.window:                                          # a global block: the 16 windows of an image are one sequence
             y = y.reshape(b, 16 * h * w, c)
         y = vit_attention(blk.attn, y, fused).reshape(b * 16, h * w, c)
-        x = x + blk.gamma_1 * y
+        dp = getattr(blk.drop_path, "drop_prob", 0.0) if training else 0.0
+        if dp > 0:
+            x = _drop_path_residual(x, y, blk.gamma_1, dp, fused, drop_path_keep, used_keep)
+        else:
+            x = x + blk.gamma_1 * y
         y = blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(x))))
-        x = x + blk.gamma_2 * y
+        if dp > 0:
+            x = _drop_path_residual(x, y, blk.gamma_2, dp, fused, drop_path_keep, used_keep)
+        else:
+            x = x + blk.gamma_2 * y
         if i in enc.out_feature_indexes:
             taps.append(x.reshape(b, 4, 4, h, w, c).permute(0, 5, 1, 3, 2, 4).reshape(b, c, hp, wp))
     return taps
@@ -147,22 +184,30 @@ def _reparam(delta, ref):
 
 
 def _refuse_training_knobs(model):
-    if getattr(model, "_drop_path_rate", 0.0) > 0:
-        raise NotImplementedError(f"lwdetr_amd: drop-path (rate {model._drop_path_rate}) is not implemented in the training forward")
+    blocks = model.backbone[0].encoder.blocks
+    if getattr(model, "_drop_path_rate", 0.0) > 0 and not any(hasattr(b.drop_path, "drop_prob") for b in blocks):
+        raise NotImplementedError(f"lwdetr_amd: drop-path (rate {model._drop_path_rate}) is not implemented in the training forward of a model "
+                                  "built without it: the reference ignores update_drop_path on such a model; build with args.drop_path > 0")
     D.refuse_dropout(model)
 
 
-def differentiable_forward(model, samples, fused=None, collect=None):
+def differentiable_forward(model, samples, fused=None, collect=None, drop_path_keep=None):
     """``LWDETR.forward`` with autograd: samples NestedTensor | list[Tensor(3, h, w)] | Tensor(B, 3, H, W) -> the reference's output dict
     (pred_logits, pred_boxes, aux_outputs, enc_outputs). ``model.training`` selects ``group_detr`` groups and batch statistics; in eval mode
-    one group runs. ``collect`` (a dict) receives ``topk_idx`` (groups, B, nq) and ``memory``."""
+    one group runs. ``collect`` (a dict) receives ``topk_idx`` (groups, B, nq), ``memory`` and ``drop_path_keep``, the list of bool (B * 16,)
+    window masks of the drop-path draws in draw order (empty when nothing was drawn). ``drop_path_keep``: None draws; a list of such masks is
+    replayed instead, and must hold exactly as many as the forward uses."""
     images, mask = _unpack(samples)
     if model.training:
         _refuse_training_knobs(model)
     groups = model.group_detr if model.training else 1
     nq, tr = model.num_queries, model.transformer
     bb = model.backbone[0]
-    levels = projector_forward(bb.projector, vit_forward(bb.encoder, images, fused), fused)
+    replay, used_keep = None if drop_path_keep is None else iter(drop_path_keep), []
+    taps = vit_forward(bb.encoder, images, fused, model.training, replay, used_keep)
+    if replay is not None and next(replay, None) is not None:
+        raise ValueError(f"drop_path_keep holds more masks than the forward draws ({len(used_keep)})")
+    levels = projector_forward(bb.projector, taps, fused)
     level_shapes = [s for _, s in levels]
     B = images.shape[0]
     memory = levels[0][0] if len(levels) == 1 else torch.cat([t for t, _ in levels], 1)
@@ -183,7 +228,7 @@ def differentiable_forward(model, samples, fused=None, collect=None):
     else:
         refpoint_ts, memory_ts, boxes_ts, idx = two_stage_select_torch(memory, mask_flatten, level_shapes, tr, nq, groups)
     if collect is not None:
-        collect.update(topk_idx=idx, memory=memory)
+        collect.update(topk_idx=idx, memory=memory, drop_path_keep=used_keep)
 
     tgt = model.query_feat.weight[:groups * nq].unsqueeze(0).repeat(B, 1, 1)
     refpoint = _reparam(model.refpoint_embed.weight[:groups * nq].unsqueeze(0).repeat(B, 1, 1), refpoint_ts.to(model.refpoint_embed.weight.dtype))

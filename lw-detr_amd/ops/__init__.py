@@ -6,5 +6,7 @@ from .functions import (MSDeformAttnFunction, ms_deform_attn_backward, ms_deform
 from .modules import MSDeformAttn  # noqa: F401
 from .train_glue import (LayerNorm2dFunction, SineEmbedFunction, layer_norm_2d, patch_layer_norm_2d,  # noqa: F401
                          query_sine_embed)
+from .drop_path import (DropPathResidualFunction, drop_path_keep, drop_path_residual, drop_path_residual_torch,  # noqa: F401
+                        drop_path_supports)
 from .decoder_train import (decoder_forward, decoder_layer_forward, grouped_self_attention, patch_decoder)  # noqa: F401
 from .two_stage import SelectRowsFunction, patch_two_stage, two_stage_scores, two_stage_select  # noqa: F401

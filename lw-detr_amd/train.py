@@ -25,7 +25,7 @@ import torch
 
 from . import _native as N
 
-__all__ = ["get_param_dict", "get_vit_lr_decay_rate", "get_vit_weight_decay_rate", "NativeAdamW", "ModelEma", "clip_grad_norm_", "CHUNK"]
+__all__ = ["get_param_dict", "get_vit_lr_decay_rate", "get_vit_weight_decay_rate", "NativeAdamW", "ModelEma", "clip_grad_norm_", "drop_scheduler", "CHUNK"]
 
 CHUNK = N.MT_CHUNK
 _TENSOR_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("ema", "<u8"), ("numel", "<i8"), ("kind", "<i4"), ("skip", "<i4"),
@@ -33,6 +33,27 @@ _TENSOR_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), (
 _CHUNK_DT = np.dtype([("tensor", "<i4"), ("count", "<i4"), ("offset", "<i8")])
 assert _TENSOR_DT.itemsize == C.sizeof(N.MtTensor) and _CHUNK_DT.itemsize == C.sizeof(N.MtChunk)
 _RING = 4
+
+
+# ------------------------------------------------------------------------------------------------ drop-rate schedule
+def drop_scheduler(drop_rate, epochs, niter_per_ep, cutoff_epoch=0, mode="standard", schedule="constant"):
+    """The per-iteration drop-path (or dropout) rate as a numpy array of epochs * niter_per_ep entries (util/drop_scheduler.py): ``standard`` holds
+    ``drop_rate`` throughout; ``early`` holds it (``constant``) or runs it down to 0 (``linear``) over the first ``cutoff_epoch`` epochs and is 0
+    afterwards; ``late`` is 0 for ``cutoff_epoch`` epochs and ``drop_rate`` afterwards. ``model.update_drop_path(schedule[it], depth)`` per step."""
+    assert mode in ("standard", "early", "late")
+    total = epochs * niter_per_ep
+    if mode == "standard":
+        return np.full(total, drop_rate)
+    head, tail = cutoff_epoch * niter_per_ep, (epochs - cutoff_epoch) * niter_per_ep
+    if mode == "early":
+        assert schedule in ("constant", "linear")
+        first = np.full(head, drop_rate) if schedule == "constant" else np.linspace(drop_rate, 0, head)
+        out = np.concatenate((first, np.full(tail, 0)))
+    else:
+        assert schedule in ("constant",)
+        out = np.concatenate((np.full(head, 0), np.full(tail, drop_rate)))
+    assert len(out) == total
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ parameter groups
